@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — benchmarks of the MI355X-native tensor-contraction engine behind the cuTENSOR C ABI.
 
-    python bench.py --gpus N --steps K --warmup W        (one JSON line on stdout)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]       (one JSON line on stdout)
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else runs.  --full adds everything
+else the benchmark measures (below: roofline, the sample's protocol, HBM-cold operands, the CPU baseline, the
+`secondary` configs and the live rocprofv3 passes).  --dump-outputs DIR writes what the timed path computed in its
+last step as DIR/<name>.npy (float32; inputs are seeded, so two builds can be compared output for output).
 
 N = 1 (BASELINE.json configs[1], the headline): einsum 'abcd,dcbe->ae', fp32, a=e=96, b=c=d=64 — the call
     sequence of cuTENSOR/einsum.cu:248-339 (descriptors -> contraction -> plan -> cutensorContract) through
     lib/libcutensor.so.  A "step" is one cutensorContract call (GETT kernel + split-K fold) on tensors resident in
     HBM; plan creation is outside the timed region, as in the samples (contraction.cu:218-222 vs :253-270).
-    The same line carries `secondary`: the other BASELINE configs measured in the same process with the samples'
+    Dumped output: C.npy, the (a, e) = (96, 96) result of the last timed step.
+    With --full the same line carries `secondary`: the other BASELINE configs measured in the same process with the samples'
     own formulas — contraction.cu default fp32 (configs[0] shape on the GPU), 2048^3 permute + reduce (configs[2]),
     bf16 8192^3 (configs[3]), cuTENSORMg on one device (configs[4] at n = 1) — each with its roofline, and
     `cold_operands_value`: the headline with four rotating (A, B) pairs (805 MB > the 256-MiB Infinity Cache).
@@ -26,6 +32,7 @@ N > 1 (BASELINE.json configs[4], north_star's "cuTENSORMg sharded case"): cutens
     sharded, RCCL all-reduce of the 36-KB result) which is reported as a secondary line (and is the fallback
     `value` if the multi-device measurement fails).  With fewer visible GPUs than requested the line says
     `"n_gpus": <used>, "requested_gpus": N`.
+    Dumped output when the cuTENSORMg contraction is `value`: mg_C_sample.npy, a fixed, seeded sample of 2^20 elements of C.
 """
 import argparse
 import ctypes
@@ -80,10 +87,11 @@ def cpu_baseline(a_np, b_np):
 # ---------------------------------------------------------------------------------------------------------
 # cuTENSORMg measurement (one process, n devices)
 # ---------------------------------------------------------------------------------------------------------
-def mg_measure(ndev, extent, steps, warmup, sample_reps=3, check=True, virtual=False):
+def mg_measure(ndev, extent, steps, warmup, sample_reps=3, check=True, virtual=False, dump_dir=None):
     """C[i,j] = A[i,k] B[k,j] fp32 through libcutensorMg on devices 0..ndev-1: i cut ndev ways (A, C row slabs), B in
     column slabs (all-gathered).  Returns a dict with the throughput of `steps` back-to-back calls and the sample's
-    protocol (wall clock + per-device sync, min of `sample_reps`)."""
+    protocol (wall clock + per-device sync, min of `sample_reps`).  With `dump_dir`, a fixed, seeded sample of C after the timed
+    calls is written to dump_dir/mg_C_sample.npy."""
     import torch
     from cudalibrarysamples_amd import cutensormg as cm
     n = ndev
@@ -135,6 +143,19 @@ def mg_measure(ndev, extent, steps, warmup, sample_reps=3, check=True, virtual=F
             call()
         sync_all()
         elapsed = time.perf_counter() - t0
+        if dump_dir:
+            # 2^20 elements of C at seeded (i, j): C[i, j] lives in row slab i // (E/n) as [j][i_local]
+            rng = np.random.default_rng(7)
+            per = E // n
+            ii, jj = rng.integers(0, E, size=1 << 20), rng.integers(0, E, size=1 << 20)
+            sample = np.empty(ii.size, dtype=np.float32)
+            for g in range(n):
+                sel = np.nonzero(ii // per == g)[0]
+                if sel.size:
+                    flat = torch.from_numpy(jj[sel] * per + ii[sel] % per).to(cells[2][g].device)
+                    sample[sel] = cells[2][g][flat].cpu().numpy()
+            os.makedirs(dump_dir, exist_ok=True)
+            np.save(os.path.join(dump_dir, "mg_C_sample.npy"), sample)
         d2 = con.describe()    # after the calls: which transport the first-two-calls trial chose
         err = None
         if check:
@@ -176,7 +197,7 @@ def mg_child_main(args):
     scaled, sample = (MG_SCALED_EXTENT, MG_SAMPLE_EXTENT) if not virtual else (4096, 2048)
     for attempt in range(2):
         try:
-            out["scaled"] = mg_measure(ndev, scaled, args.steps, args.warmup, virtual=virtual)
+            out["scaled"] = mg_measure(ndev, scaled, args.steps, args.warmup, virtual=virtual, dump_dir=args.dump_outputs)
             out["sample"] = mg_measure(ndev, sample, max(20, min(args.steps, 200)), 3, virtual=virtual)
             if ndev > 1:   # the same problems on one device, same process: the base of the strong-scaling speedup
                 out["scaled_1"] = mg_measure(1, scaled, 3, 1, check=False)
@@ -194,7 +215,7 @@ def mg_child_main(args):
     print("MGCHILD " + json.dumps(out), flush=True)
 
 
-def run_mg_child(ndev, steps, warmup, timeout_s, virtual=False, extra_env=None):
+def run_mg_child(ndev, steps, warmup, timeout_s, virtual=False, extra_env=None, dump_dir=None):
     env = dict(os.environ)
     env.update(extra_env or {})
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "ROLE_RANK", "LOCAL_WORLD_SIZE",
@@ -204,6 +225,8 @@ def run_mg_child(ndev, steps, warmup, timeout_s, virtual=False, extra_env=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--mg-child", str(ndev), "--steps", str(steps), "--warmup", str(warmup)]
     if virtual:
         cmd.append("--mg-virtual")
+    if dump_dir:
+        cmd += ["--dump-outputs", dump_dir]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env, cwd=ROOT)
     except subprocess.TimeoutExpired:
@@ -283,7 +306,7 @@ def live_pmc_traffic(timeout_s=150):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "-d", out, "-o", "r", "--", sys.executable, os.path.abspath(__file__), "--steps", "100", "--warmup", "10",
-                   "--no-cpu", "--no-secondary", "--no-pmc", "--burn-in-ms", "0"]
+                   "--full", "--no-cpu", "--no-secondary", "--no-pmc", "--burn-in-ms", "0"]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env, cwd="/tmp")
             dbs = glob.glob(os.path.join(out, "**", "*.db"), recursive=True)
             if r.returncode != 0 or not dbs:
@@ -935,6 +958,11 @@ def main():
                     help="untimed device clock ramp before the warmup steps: MI355X needs ~15-20 ms of sustained load "
                          "before it settles into its steady clock state (profiles/r01e_long_run_timeline.txt)")
     ap.add_argument("--algo", type=str, default="default", help="default | patient | <candidate index>")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline, the sample's protocol, HBM-cold operands, the CPU "
+                         "baseline, the secondary configs and the live rocprofv3 passes (the --no-* switches below trim it)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="headline only (profiling runs)")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the two live rocprofv3 --pmc passes for roofline.traffic (the committed "
@@ -950,6 +978,8 @@ def main():
                     help="self-test of the N > 1 path on a box with fewer GPUs: the N devices are N logical devices on GPU 0 and the "
                          "shapes are shrunk; the line then says n_gpus = 1 and the numbers are not scaling results")
     args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)     # the cuTENSORMg child runs from the repository root
 
     import torch
     import torch.distributed as dist
@@ -996,12 +1026,12 @@ def main():
     mg_devices = requested if args.mg_virtual else min(requested, visible)
     if requested > 1 and not args.einsum_only:
         if rank == 0 and mg_devices > 1:
-            mg = run_mg_child(mg_devices, args.steps, args.warmup, args.mg_timeout, virtual=args.mg_virtual)
+            mg = run_mg_child(mg_devices, args.steps, args.warmup, args.mg_timeout, virtual=args.mg_virtual, dump_dir=args.dump_outputs)
             if "timed out" in str(mg.get("error", "")) and os.environ.get("CUTENSORMG_AMD_TRANSPORT") != "peer":
                 # a hang (killed by the timeout) in the RCCL path: one more child with peer copies instead
                 first = mg["error"]
                 os.environ["CUTENSORMG_AMD_TRANSPORT"] = "peer"
-                mg = run_mg_child(mg_devices, args.steps, args.warmup, args.mg_timeout, virtual=args.mg_virtual)
+                mg = run_mg_child(mg_devices, args.steps, args.warmup, args.mg_timeout, virtual=args.mg_virtual, dump_dir=args.dump_outputs)
                 mg["first_attempt_error"] = first
         if world > 1:
             dist.barrier(group=cpu_group)   # CPU-side wait: the other ranks' GPUs stay idle during the measurement
@@ -1093,12 +1123,14 @@ def main():
     einsum_ms = elapsed / args.steps * 1e3
     einsum_value = world * FLOP / (elapsed / args.steps) / 1e9
     einsum_1gpu_value = einsum_value / world   # per-GPU rate of the headline at this rank count (= the headline itself at N = 1)
+    # the result of the last timed step (after the fence: folded over the ranks), before anything below reuses the buffers
+    last_out = outs[(args.steps - 1) % nbuf].cpu().numpy() if (args.dump_outputs and rank == 0 and args.steps > 0) else None
 
     roof = cpu = None
     secondary = []
     cold = None
     sample_protocol = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: one HIP event pair on the launch stream -----------------------------------
         # GETT kernel alone, in the same steady state as the timed loop: the fold is switched off (per-handle diagnostic),
         # `n` launches go out back to back (rocprofv3 shows < 0.05 us between them) and ONE HIP event pair on the launch
@@ -1171,7 +1203,7 @@ def main():
         roof["frac_event_pair"], roof["achieved_event_pair"] = roof["frac"], roof["achieved"]
         roof["frac_source"] = "event pair (no live rocprofv3 pass in this run)"
         if world == 1 and not args.no_pmc and not args.no_secondary and not args.einsum_only:
-            prof = live_profile_of([sys.executable, os.path.abspath(__file__), "--steps", "200", "--warmup", "20", "--no-cpu", "--no-secondary",
+            prof = live_profile_of([sys.executable, os.path.abspath(__file__), "--steps", "200", "--warmup", "20", "--full", "--no-cpu", "--no-secondary",
                                     "--no-pmc", "--no-cold"], "%gett_f32_stream_kernel%")
             if prof and prof.get("kernel_avg_us"):
                 roof["achieved"] = FLOP / (prof["kernel_avg_us"] * 1e-6) / 1e12
@@ -1391,6 +1423,15 @@ def main():
         }
         if use_mg:
             line["headline_kernel_roofline"] = roof
+        if args.dump_outputs:
+            # the cuTENSORMg child wrote its sample already; when the einsum is `value`, its result is the output instead
+            mg_file = os.path.join(args.dump_outputs, "mg_C_sample.npy")
+            if not use_mg:
+                if os.path.exists(mg_file):
+                    os.remove(mg_file)
+                if last_out is not None:
+                    os.makedirs(args.dump_outputs, exist_ok=True)
+                    np.save(os.path.join(args.dump_outputs, "C.npy"), last_out.astype(np.float32))
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

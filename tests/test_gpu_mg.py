@@ -193,7 +193,7 @@ def test_mg_free_mode_shard_layout(mg, monkeypatch, n, E, beta, env):
             np.testing.assert_allclose(got, ref, rtol=1e-4, err_msg=str(d)[:400])
 
 
-def test_bench_multi_device_path_self_test(built):
+def test_bench_multi_device_path_self_test(built, tmp_path):
     """bench.py --gpus N on a box with fewer GPUs than N: `--mg-virtual` drives the whole N > 1 path of the benchmark — child
     process, cuTENSORMg over N (logical) devices, result check, speedup bookkeeping, JSON assembly — on GPU 0."""
     import json
@@ -202,7 +202,7 @@ def test_bench_multi_device_path_self_test(built):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--mg-virtual", "--steps", "3", "--warmup", "1", "--no-cpu",
-                        "--no-secondary", "--burn-in-ms", "0"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--no-secondary", "--burn-in-ms", "0", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["requested_gpus"] == 4 and line["n_gpus"] == 1 and line["scaling"] == "strong", line
@@ -214,6 +214,10 @@ def test_bench_multi_device_path_self_test(built):
     assert line["speedup_vs_1_same_workload"] == line["config"]["speedup_vs_1"] and line["einsum_value"] > 0 and line["rccl_ranks_seen"] == 1
     kinds = [s["workload"] for s in line["secondary"]]
     assert any("4096^3" in k or "2048^3" in k for k in kinds) and any("einsum.cu" in k for k in kinds), kinds
+    # --dump-outputs: the cuTENSORMg result is `value`, so its seeded sample of C is the output (U(0,1) operands, K = 4096: C > 0)
+    sample = np.load(str(tmp_path / "mg_C_sample.npy"))
+    assert sample.dtype == np.float32 and sample.shape == (1 << 20,) and np.all(np.isfinite(sample)) and sample.min() > 0
+    assert not (tmp_path / "C.npy").exists()
     # and with one visible GPU and no self-test switch the line says so instead of pretending
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-secondary",
                         "--burn-in-ms", "0"], capture_output=True, text=True, timeout=900, cwd=root)

@@ -35,9 +35,9 @@ run_bench() {   # run_bench <name> <gpus> [env...]
   local name=$1 n=$2; shift 2
   if [ "$n" -gt 1 ]; then
     x env "$@" timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 400)) \
-        bench.py --gpus "$n" --steps "$STEPS" --warmup 5 > "$OUT/$name.json" 2> "$OUT/$name.err"
+        bench.py --gpus "$n" --steps "$STEPS" --warmup 5 --full > "$OUT/$name.json" 2> "$OUT/$name.err"
   else
-    x env "$@" timeout 1200 python bench.py --gpus 1 --steps "$STEPS" --warmup 5 > "$OUT/$name.json" 2> "$OUT/$name.err"
+    x env "$@" timeout 1200 python bench.py --gpus 1 --steps "$STEPS" --warmup 5 --full > "$OUT/$name.json" 2> "$OUT/$name.err"
   fi
   [ "$DRY" = 1 ] && return 0
   python - "$OUT/$name.json" "$name" >> "$OUT/summary.txt" <<'PY'
@@ -65,7 +65,7 @@ if [ "$NGPU" -ge 2 ]; then
   # 4. gather waves
   for w in 1 2 4; do run_bench "bench_gpus${N}_waves_$w" "$N" CUTENSORMG_AMD_WAVES=$w; done
   # 5. kernel trace
-  (cd /tmp && x timeout 1200 rocprofv3 --kernel-trace --stats -d "$OUT/trace_gpus$N" -o r -- python "$ROOT/bench.py" --gpus "$N" --steps 10 --warmup 2 > "$OUT/trace_gpus$N.log" 2>&1)
+  (cd /tmp && x timeout 1200 rocprofv3 --kernel-trace --stats -d "$OUT/trace_gpus$N" -o r -- python "$ROOT/bench.py" --gpus "$N" --steps 10 --warmup 2 --full > "$OUT/trace_gpus$N.log" 2>&1)
   f=$(find "$OUT/trace_gpus$N" -name '*.db' 2>/dev/null | head -1)
   [ "$DRY" = 1 ] && f=trace.db
   [ -n "$f" ] && x python tools/rocprof_summary.py "$f" > "$PROF/${TAG}_trace_gpus$N.summary.txt" 2>&1

@@ -99,12 +99,12 @@ python tools/bench_bandwidth.py --n 1024 --check > $OUT/bandwidth_1024.jsonl 2>/
 samples/bin/einsum --flow --calls 2000 > $OUT/einsum_flow_plan_per_call.jsonl 2>/dev/null
 cd /tmp
 # ---- 3. the whole default bench line (secondary configs included): kernel trace only ------------------------------------
-rocprofv3 --kernel-trace --stats -d $OUT/bench_all_trace -o r -- python $ROOT/bench.py --steps 200 --warmup 20 --no-cpu > $OUT/bench_all_trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/bench_all_trace -o r -- python $ROOT/bench.py --steps 200 --warmup 20 --full --no-cpu > $OUT/bench_all_trace.log 2>&1
 summ bench_all_trace bench_all_trace
 # ---- 4. un-profiled reference lines ------------------------------------------------------------------------------------
 cd $ROOT
-python bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.log 2>&1
-python bench.py > $OUT/bench_default.log 2>&1
+python bench.py --steps 20 --warmup 5 --full > $OUT/bench_steps20.log 2>&1
+python bench.py --full > $OUT/bench_default.log 2>&1
 find $OUT -name '*.csv' -size +1M -delete
 find $OUT -name '*.db' -delete
 rm -rf $OUT/einsum/trace $OUT/einsum/pmc_sq $OUT/einsum/pmc_fetch $OUT/einsum/pmc_write
