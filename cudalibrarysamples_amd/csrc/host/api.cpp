@@ -1,6 +1,7 @@
 // api.cpp — the exported cuTENSOR C ABI (include/cutensor.h) on top of the planners and the
 // gfx950 kernels.  Each entry point cites the reference call site it serves.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -303,10 +304,12 @@ struct LoneSplit {
     cutensorOperationDescriptor inner, redA, redB;
     bool hasA = false, hasB = false;
     uint64_t bytesA = 0, bytesB = 0;       // packed sizes of the temporaries
+    int64_t summedA = 1, summedB = 1;      // elements summed into each element of a temporary
 };
 static bool split_lone_modes(const cutensorOperationDescriptor& desc, LoneSplit& out) {
     auto has = [](const std::vector<int32_t>& v, int32_t l) { return std::find(v.begin(), v.end(), l) != v.end(); };
-    auto reduce_operand = [&](const TensorUse& X, const TensorUse& other, cutensorOperationDescriptor& red, TensorUse& kept, uint64_t& bytes) {
+    auto reduce_operand = [&](const TensorUse& X, const TensorUse& other, cutensorOperationDescriptor& red, TensorUse& kept, uint64_t& bytes,
+                              int64_t& summed) {
         bool lone = false;
         for (size_t i = 0; i < X.modes.size(); ++i)
             if (X.desc.extent[i] != 1 && !has(other.modes, X.modes[i]) && !has(desc.C.modes, X.modes[i])) lone = true;
@@ -317,8 +320,9 @@ static bool split_lone_modes(const cutensorOperationDescriptor& desc, LoneSplit&
         kept.desc.dtype = X.desc.dtype;
         kept.desc.alignment = 128;                              // a piece of the workspace at a multiple of 256 bytes: as aligned as the workspace itself (contraction.cu:242 asserts 128)
         int64_t run = 1;
+        summed = 1;
         for (size_t i = 0; i < X.modes.size(); ++i) {
-            if (!has(other.modes, X.modes[i]) && !has(desc.C.modes, X.modes[i])) continue;   // summed away (extent-1 lone modes too)
+            if (!has(other.modes, X.modes[i]) && !has(desc.C.modes, X.modes[i])) { summed *= X.desc.extent[i]; continue; }   // summed away (extent-1 lone modes too)
             kept.modes.push_back(X.modes[i]);
             kept.desc.extent.push_back(X.desc.extent[i]);
             kept.desc.stride.push_back(run);
@@ -338,8 +342,8 @@ static bool split_lone_modes(const cutensorOperationDescriptor& desc, LoneSplit&
         return true;
     };
     TensorUse keptA, keptB;
-    out.hasA = reduce_operand(desc.A, desc.B, out.redA, keptA, out.bytesA);
-    out.hasB = reduce_operand(desc.B, desc.A, out.redB, keptB, out.bytesB);
+    out.hasA = reduce_operand(desc.A, desc.B, out.redA, keptA, out.bytesA, out.summedA);
+    out.hasB = reduce_operand(desc.B, desc.A, out.redB, keptB, out.bytesB, out.summedB);
     if (!out.hasA && !out.hasB) return false;
     out.inner = desc;
     if (out.hasA) out.inner.A = keptA;
@@ -1043,21 +1047,21 @@ cutensorStatus_t cutensorEstimateWorkspaceSize(const cutensorHandle_t handle, co
         *workspaceSizeEstimate = ((desc->tBytes + 255) & ~255ull) + std::max(w1, w2);
         return CUTENSOR_STATUS_SUCCESS;
     }
+    if (desc->kind == OpKind::Contraction) {
+        LoneSplit ls;     // the temporaries + the largest need of the reductions and the inner contraction — at WORKSPACE_MIN too: the
+        if (split_lone_modes(*desc, ls)) {     // temporaries are mandatory (the reference binding re-plans at MIN: einsum.cc:110)
+            uint64_t wI = 0, wA = 0, wB = 0;
+            cutensorStatus_t st = cutensorEstimateWorkspaceSize(handle, &ls.inner, planPref, workspacePref, &wI);
+            if (st == CUTENSOR_STATUS_SUCCESS && ls.hasA) st = cutensorEstimateWorkspaceSize(handle, &ls.redA, planPref, workspacePref, &wA);
+            if (st == CUTENSOR_STATUS_SUCCESS && ls.hasB) st = cutensorEstimateWorkspaceSize(handle, &ls.redB, planPref, workspacePref, &wB);
+            if (st != CUTENSOR_STATUS_SUCCESS) return st;
+            *workspaceSizeEstimate = ((ls.bytesA + 255) & ~255ull) + ((ls.bytesB + 255) & ~255ull) + std::max(wI, std::max(wA, wB));
+            return CUTENSOR_STATUS_SUCCESS;
+        }
+    }
     if (workspacePref == CUTENSOR_WORKSPACE_MIN) return CUTENSOR_STATUS_SUCCESS;
     const uint64_t cap = (workspacePref == CUTENSOR_WORKSPACE_MAX) ? (4ull << 30) : (1ull << 30);
     if (desc->kind == OpKind::Contraction) {
-        {
-            LoneSplit ls;     // the temporaries + the largest need of the reductions and the inner contraction
-            if (split_lone_modes(*desc, ls)) {
-                uint64_t wI = 0, wA = 0, wB = 0;
-                cutensorStatus_t st = cutensorEstimateWorkspaceSize(handle, &ls.inner, planPref, workspacePref, &wI);
-                if (st == CUTENSOR_STATUS_SUCCESS && ls.hasA) st = cutensorEstimateWorkspaceSize(handle, &ls.redA, planPref, workspacePref, &wA);
-                if (st == CUTENSOR_STATUS_SUCCESS && ls.hasB) st = cutensorEstimateWorkspaceSize(handle, &ls.redB, planPref, workspacePref, &wB);
-                if (st != CUTENSOR_STATUS_SUCCESS) return st;
-                *workspaceSizeEstimate = ((ls.bytesA + 255) & ~255ull) + ((ls.bytesB + 255) & ~255ull) + std::max(wI, std::max(wA, wB));
-                return CUTENSOR_STATUS_SUCCESS;
-            }
-        }
         ContractionView v;
         cutensorStatus_t st = build_contraction_view(*desc, v, nullptr);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
@@ -1430,6 +1434,11 @@ cutensorStatus_t cutensorCreatePlan(const cutensorHandle_t handle, cutensorPlan_
             if (st != CUTENSOR_STATUS_SUCCESS) { delete pi; delete pa; delete pb; return st; }
             pl->sub1 = pi; pl->loneA = pa; pl->loneB = pb;
             pl->loneBytesA = ls.bytesA; pl->loneBytesB = ls.bytesB;
+            if (desc->A.desc.dtype == HIP_R_16F && desc->scalarType == HIP_R_32F) {   // (loneShiftA: internal.hpp)
+                auto ceil_log2 = [](int64_t n) { int s = 0; while ((int64_t{1} << s) < n) ++s; return s; };
+                pl->loneShiftA = ls.hasA ? (ceil_log2(ls.summedA) + 1) / 2 : 0;
+                pl->loneShiftB = ls.hasB ? (ceil_log2(ls.summedB) + 1) / 2 : 0;
+            }
             pl->choice = ContractionChoice{};
             pl->choice.kernel = -4;
             pl->requiredWorkspace = offW + std::max<uint64_t>(pi->requiredWorkspace, std::max<uint64_t>(pa ? pa->requiredWorkspace : 0, pb ? pb->requiredWorkspace : 0));
@@ -1826,20 +1835,24 @@ cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorP
         const void* zero = wideScalar ? static_cast<const void*>(zerod) : static_cast<const void*>(zerof);
         const void* a = A;
         const void* bb = B;
+        // fp16 temporaries (float scalars): scaled down by exact powers of two, alpha scaled up by their product (loneShiftA: internal.hpp)
+        const float scaleA = std::ldexp(1.f, -plan->loneShiftA), scaleB = std::ldexp(1.f, -plan->loneShiftB);
+        const bool scaled = plan->loneShiftA + plan->loneShiftB > 0;
+        const float alphaScaled = scaled ? *static_cast<const float*>(alpha) * std::ldexp(1.f, plan->loneShiftA + plan->loneShiftB) : 0.f;
         cutensorStatus_t st = CUTENSOR_STATUS_SUCCESS;
         // (the first step of an operand is a reduction over its lone modes, or — plan_repack — a permuted copy into a packed temporary)
         if (plan->loneA) {
             st = plan->loneA->kind == OpKind::Permutation ? cutensorPermute(handle, plan->loneA, one, A, ws, stream)
-                                                         : cutensorReduce(handle, plan->loneA, one, A, zero, ws, ws, ws + offW, workspaceSize - offW, stream);
+                                                         : cutensorReduce(handle, plan->loneA, scaled ? &scaleA : one, A, zero, ws, ws, ws + offW, workspaceSize - offW, stream);
             a = ws;
         }
         if (st == CUTENSOR_STATUS_SUCCESS && plan->loneB) {
             st = plan->loneB->kind == OpKind::Permutation ? cutensorPermute(handle, plan->loneB, one, B, ws + offB, stream)
-                                                         : cutensorReduce(handle, plan->loneB, one, B, zero, ws + offB, ws + offB, ws + offW, workspaceSize - offW, stream);
+                                                         : cutensorReduce(handle, plan->loneB, scaled ? &scaleB : one, B, zero, ws + offB, ws + offB, ws + offW, workspaceSize - offW, stream);
             bb = ws + offB;
         }
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
-        return cutensorContract(handle, plan->sub1, alpha, a, bb, beta, C, D, ws + offW, workspaceSize - offW, stream);
+        return cutensorContract(handle, plan->sub1, scaled ? &alphaScaled : alpha, a, bb, beta, C, D, ws + offW, workspaceSize - offW, stream);
     }
     if (plan->choice.kernel == -3) {
         // peeled contraction: every index combination of the peeled modes is one launch of the inner plan on offset operands;
@@ -2150,7 +2163,7 @@ cutensorStatus_t cutensorContractTrinary(const cutensorHandle_t handle, const cu
     if (plan == nullptr || plan->kind != OpKind::ContractionTrinary || plan->sub1 == nullptr || plan->sub2 == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
     if (alpha == nullptr || beta == nullptr || A == nullptr || B == nullptr || C == nullptr || E == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
     if (workspace == nullptr || workspaceSize < plan->requiredWorkspace) return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;
-    if (misaligned(workspace, 256)) return CUTENSOR_STATUS_INVALID_VALUE;
+    if (misaligned(workspace, 128)) return CUTENSOR_STATUS_INVALID_VALUE;   // the intermediate and the sub-plans ask for 128 (contraction.cu:242 asserts no more)
     const void* in[3] = {A, B, C};
     const void *X = in[plan->triOrder[0]], *Y = in[plan->triOrder[1]], *Z = in[plan->triOrder[2]];
     const uint64_t tOff = (plan->tBytes + 255) & ~255ull;
@@ -2263,11 +2276,16 @@ void ctamdPlanMemoStats(const cutensorHandle_t handle, uint64_t* hits, uint64_t*
 int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     if (plan == nullptr || buf == nullptr || len == 0) return -1;
     int n = 0;
+    if (plan->kind == OpKind::BlockSparseContraction) return blocksparse_describe(*plan, buf, len);
+    if (plan->kind == OpKind::ContractionTrinary)
+        return std::snprintf(buf, len, "{\"op\":\"contraction_trinary\",\"intermediate_bytes\":%llu,\"workspace\":%llu}",
+                             (unsigned long long)plan->tBytes, (unsigned long long)plan->requiredWorkspace);
     if (plan->kind == OpKind::Contraction && plan->choice.kernel == -3 && plan->sub1 != nullptr) {
-        // peeled contraction: the inner (tiled) plan's description with the peel in front
+        // peeled contraction: the inner (tiled) plan's description with the peel in front (and how many peeled modes are contracted ones)
         long long launches = 1;
-        for (const PeelMode& pm : plan->peel) launches *= pm.extent;
-        n = std::snprintf(buf, len, "{\"peeled_modes\":%zu,\"peel_launches\":%lld,", plan->peel.size(), launches);
+        int contracted = 0;
+        for (const PeelMode& pm : plan->peel) { launches *= pm.extent; contracted += pm.contracted ? 1 : 0; }
+        n = std::snprintf(buf, len, "{\"peeled_modes\":%zu,\"peeled_contracted\":%d,\"peel_launches\":%lld,", plan->peel.size(), contracted, launches);
         if (n < 0 || (size_t)n >= len) return -1;
         const int m = ctamdDescribePlan(plan->sub1, buf + n - 1, len - (size_t)n + 1);   // overwrite our '{' + keep theirs: splice below
         if (m < 0) return -1;

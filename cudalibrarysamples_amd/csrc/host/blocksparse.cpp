@@ -13,6 +13,7 @@
 // carries the caller's beta, the following ones beta = 1; output blocks without any contribution are scaled by
 // beta (or cleared).  Work is issued block pair by block pair on the caller's stream.
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -205,6 +206,12 @@ cutensorStatus_t blocksparse_plan(cutensorHandle_t handle, const cutensorOperati
     pl->dtype = desc.bs->D.dtype;
     pl->requiredWorkspace = need;
     return CUTENSOR_STATUS_SUCCESS;
+}
+
+int blocksparse_describe(const cutensorPlan& pl, char* buf, size_t len) {
+    if (!pl.bsp) return -1;
+    return std::snprintf(buf, len, "{\"op\":\"blocksparse\",\"tasks\":%zu,\"dense_plans\":%zu,\"workspace\":%llu}", pl.bsp->tasks.size(),
+                         pl.bsp->plans.size(), (unsigned long long)pl.requiredWorkspace);
 }
 
 }  // namespace ctamd

@@ -175,6 +175,7 @@ cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t 
 
 cutensorStatus_t blocksparse_estimate(cutensorHandle_t handle, const cutensorOperationDescriptor& desc, uint64_t* ws);
 cutensorStatus_t blocksparse_plan(cutensorHandle_t handle, const cutensorOperationDescriptor& desc, uint64_t wsLimit, cutensorPlan* pl);
+int blocksparse_describe(const cutensorPlan& pl, char* buf, size_t len);   // ctamdDescribePlan of a block-sparse plan
 
 FastDiv make_fastdiv(uint32_t d);
 size_t  dtype_size(hipDataType t);
@@ -215,6 +216,12 @@ struct cutensorPlan {
     cutensorPlan* loneA = nullptr;
     cutensorPlan* loneB = nullptr;
     uint64_t    loneBytesA = 0, loneBytesB = 0;
+    // fp16 reductions: the temporary holds sum * 2^-loneShift, loneShift = ceil(log2(n) / 2) for n summed elements, and the inner
+    // contraction's alpha takes 2^(loneShiftA + loneShiftB) back (both factors exact).  Half the exponent of n, not all of it: a coherent
+    // sum (n |x|) lands at sqrt(n) |x| — 65504 is reached only by inputs sqrt(n) times larger than an unscaled sum needs to overflow — and
+    // a zero-mean sum (sqrt(n) |x|) stays at |x|, as precise as the inputs.  The full 2^-ceil(log2 n) would put a zero-mean temporary
+    // sqrt(n) below the inputs, into the fp16 subnormals already at |x| ~ 1e-2, n ~ 1e5 (tests/test_gpu_lone_modes.py measures both)
+    int         loneShiftA = 0, loneShiftB = 0;
     uint64_t    tBytes = 0;
     int         triOrder[3] = {0, 1, 2};
     OpKind      kind;

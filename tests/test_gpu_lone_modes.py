@@ -35,47 +35,117 @@ CASES = [  # equation (row-major framework form), shapes
 ]
 
 
-@pytest.mark.parametrize("dtype", ["float32", "float16", "complex64"])
+# rtol of one call and of the alpha / beta call: fp32 / complex64 as before (oracle); bf16: the temporary and the output are each rounded to
+# 8 bits (2 x 2^-9, tests/test_gpu_h16_unaligned.py's 8e-3); fp64 / complex128 1e-12
+RTOL = {"float32": (1e-4, 1e-4), "float16": (2e-3, 3e-3), "complex64": (1e-4, 1e-4), "bfloat16": (8e-3, 8e-3), "float64": (1e-12, 1e-12),
+        "complex128": (1e-12, 1e-12)}
+
+
+def _rounded(rng, shape, dtype, torch):
+    """U(0, 1) (complex: both parts) rounded once to the data type, as (numpy copy in a type numpy has, device tensor)"""
+    x = rng.random(shape)
+    if dtype.startswith("complex"):
+        x = x + 1j * rng.random(shape)
+    t = torch.from_numpy(np.ascontiguousarray(x)).to(getattr(torch, dtype))
+    return (t.to(torch.float32) if dtype == "bfloat16" else t).numpy(), t.cuda()
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float16", "complex64", "bfloat16", "float64", "complex128"])
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_lone_modes_through_the_c_abi_against_the_oracle(env, case, dtype):
     import oracle
     torch, ct, ops, h = env
     eq, sa, sb = case
     rng = np.random.default_rng(abs(hash((eq, dtype))) % 1000)
-    np_dt = {"float32": np.float32, "float16": np.float16, "complex64": np.complex64}[dtype]
-    a = rng.random(sa).astype(np_dt)
-    b = rng.random(sb).astype(np_dt)
-    if dtype == "complex64":
-        a = (a + 1j * rng.random(sa)).astype(np_dt)
-        b = (b + 1j * rng.random(sb)).astype(np_dt)
+    a, dA = _rounded(rng, sa, dtype, torch)
+    b, dB = _rounded(rng, sb, dtype, torch)
     p = oracle.einsum_parse(eq, sa, sb)
     assert p is not None
-    cdt = {"float32": ct.R_32F, "float16": ct.R_16F, "complex64": ct.C_32F}[dtype]
+    cdt = {"float32": ct.R_32F, "float16": ct.R_16F, "complex64": ct.C_32F, "bfloat16": ct.R_16BF, "float64": ct.R_64F, "complex128": ct.C_64F}[dtype]
     plan = ops.contraction_plan(h, p["extentA"], p["modesA"], p["extentB"], p["modesB"], p["extentC"], p["modesC"], dtype=cdt, workspace_limit=1 << 28)
     d = plan.describe()
     assert d.get("lone_reduce_A", 0) + d.get("lone_reduce_B", 0) >= 1, d
     assert plan.required_workspace >= 256 and plan.required_workspace <= plan.workspace_estimate + (1 << 20)
-    dA, dB = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     out = torch.full(p["output_shape"] or [1], float("nan"), dtype=dA.dtype, device="cuda")
     ws = torch.empty(plan.required_workspace, dtype=torch.uint8, device="cuda")
     plan.contract(1.0, dA.data_ptr(), dB.data_ptr(), 0.0, out.data_ptr(), out.data_ptr(), ws.data_ptr(), plan.required_workspace)
     torch.cuda.synchronize()
-    got = out.cpu().numpy().reshape(p["output_shape"])
-    if dtype == "float16":
-        want = np.einsum(eq, a.astype(np.float64), b.astype(np.float64))
-        # the temporary is rounded to fp16 once more than a fused sum would be: rtol 2 x 2^-11 + the output's own rounding
-        np.testing.assert_allclose(got.astype(np.float64), want, rtol=2e-3)
-    else:
+    wide = np.complex128 if dtype.startswith("complex") else np.float64
+    got = out.cpu().to(torch.float32 if dtype == "bfloat16" else out.dtype).numpy().reshape(p["output_shape"])
+    if dtype in ("float32", "complex64"):
         want = oracle.einsum(eq, a, b)
-        np.testing.assert_allclose(got, want, rtol=1e-4)
+        np.testing.assert_allclose(got, want, rtol=RTOL[dtype][0])
+    else:
+        # 16-bit: the temporary is rounded to the data type once more than a fused sum would be: rtol 2 x half an ulp + the output's own
+        want = np.einsum(eq, a.astype(wide), b.astype(wide))
+        np.testing.assert_allclose(got.astype(wide), want, rtol=RTOL[dtype][0])
     # alpha / beta ride on the inner contraction
-    c0 = torch.from_numpy(rng.random(p["output_shape"] or [1]).astype(np_dt)).cuda()
+    c0h, c0 = _rounded(rng, p["output_shape"] or [1], dtype, torch)
     out2 = c0.clone()
     plan.contract(0.5, dA.data_ptr(), dB.data_ptr(), 2.0, c0.data_ptr(), out2.data_ptr(), ws.data_ptr(), plan.required_workspace)
     torch.cuda.synchronize()
-    want2 = 0.5 * np.einsum(eq, a.astype(np.complex128 if dtype == "complex64" else np.float64), b.astype(np.complex128 if dtype == "complex64" else np.float64)) + \
-        2.0 * c0.cpu().numpy().reshape(p["output_shape"])
-    np.testing.assert_allclose(out2.cpu().numpy().reshape(p["output_shape"]), want2, rtol=3e-3 if dtype == "float16" else 1e-4)
+    want2 = 0.5 * np.einsum(eq, a.astype(wide), b.astype(wide)) + 2.0 * c0h.astype(wide).reshape(p["output_shape"])
+    np.testing.assert_allclose(out2.cpu().to(torch.float32 if dtype == "bfloat16" else out2.dtype).numpy().reshape(p["output_shape"]), want2,
+                               rtol=RTOL[dtype][1])
+    plan.destroy()
+
+
+def test_long_zero_mean_lone_mode_in_fp16(env):
+    """The other side of the fp16 temporary's scale: zero-mean A (|a| <= 4e-3) over j = 100 000.  The sum grows like sqrt(j) (~0.7), and the
+    scaled temporary must stay in fp16's normal range (2^-14 and up) so that it is as precise as an unscaled one.  Each element of D is
+    checked against its own error bound: 2 x 2^-11 of sum_k |T[i, k]| |b[k, l]| (T the exact sum over j) — a temporary scaled by
+    2^-ceil(log2 j) sits in the subnormals here and misses it."""
+    torch, ct, ops, h = env
+    eq, sa, sb = "ijk,kl->il", (6, 100000, 8), (8, 5)
+    g = torch.Generator()
+    g.manual_seed(4)
+    A = ((torch.rand(sa, generator=g, dtype=torch.float64) * 2 - 1) * 4e-3).to(torch.float16)
+    B = (torch.rand(sb, generator=g, dtype=torch.float64) + 0.5).to(torch.float16)
+    T = A.double().sum(1)
+    want = T @ B.double()
+    bound = 2 * 2.0 ** -11 * (T.abs() @ B.double().abs()) + 2.0 ** -24
+    plan = ops.contraction_plan(h, list(reversed(sa)), "kji", list(reversed(sb)), "lk", [5, 6], "li", dtype=ct.R_16F)
+    assert plan.describe()["lone_reduce_A"] == 1, plan.describe()
+    dA, dB = A.cuda(), B.cuda()
+    out = torch.full((6, 5), float("nan"), dtype=torch.float16, device="cuda")
+    ws = torch.empty(max(plan.required_workspace, 1), dtype=torch.uint8, device="cuda")
+    plan.contract(1.0, dA.data_ptr(), dB.data_ptr(), 0.0, out.data_ptr(), out.data_ptr(), ws.data_ptr(), plan.required_workspace)
+    torch.cuda.synchronize()
+    err = (out.cpu().double() - want).abs()
+    assert bool((err <= bound).all()), (float((err / bound).max()), err, bound)
+    plan.destroy()
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
+def test_long_lone_mode_in_16_bit_data(env, dtype):
+    """'ijk,kl->il' with j = 100 000 and A in [0.5, 1.5]: the sum over j (~1e5) is far beyond fp16's 65504 while the contracted result
+    (|b| ~ 1e-3) is ~800.  The fp16 temporary holds the sum scaled by 2^-ceil(log2(j) / 2) and the inner contraction's alpha scales it back
+    (csrc/host/api.cpp, loneShiftA); bf16 has the range, this is its precision over a long lone mode.  Against fp64 on the rounded inputs
+    at the tolerances of the test above."""
+    torch, ct, ops, h = env
+    eq, sa, sb = "ijk,kl->il", (6, 100000, 8), (8, 5)
+    g = torch.Generator()
+    g.manual_seed(3)
+    tdt = getattr(torch, dtype)
+    A = (torch.rand(sa, generator=g, dtype=torch.float64) + 0.5).to(tdt)
+    B = (torch.rand(sb, generator=g, dtype=torch.float64) * 1e-3 + 5e-4).to(tdt)
+    want = torch.einsum(eq, A.double(), B.double())
+    assert float(A.double().sum(1).max()) > 65504.0 and float(want.abs().max()) < 2000.0
+    cdt = ct.R_16F if dtype == "float16" else ct.R_16BF
+    # cuTENSOR modes are the row-major ones reversed (first mode fastest)
+    plan = ops.contraction_plan(h, list(reversed(sa)), "kji", list(reversed(sb)), "lk", [5, 6], "li", dtype=cdt)
+    assert plan.describe()["lone_reduce_A"] == 1, plan.describe()
+    dA, dB = A.cuda(), B.cuda()
+    out = torch.full((6, 5), float("nan"), dtype=tdt, device="cuda")
+    ws = torch.empty(max(plan.required_workspace, 1), dtype=torch.uint8, device="cuda")
+    for alpha, beta in ((1.0, 0.0), (0.5, 2.0)):
+        plan.contract(alpha, dA.data_ptr(), dB.data_ptr(), beta, out.data_ptr(), out.data_ptr(), ws.data_ptr(), plan.required_workspace)
+        torch.cuda.synchronize()
+        got = out.cpu().double()
+        assert bool(torch.isfinite(got).all()), got
+        ref = want if beta == 0.0 else alpha * want + beta * ref_prev
+        torch.testing.assert_close(got, ref, rtol=2e-3 if dtype == "float16" else 8e-3, atol=0.0)
+        ref_prev = got
     plan.destroy()
 
 

@@ -129,6 +129,31 @@ def test_contraction_trinary(env, beta):
     np.testing.assert_allclose(got, ref, rtol=1e-4)
 
 
+def test_contraction_trinary_workspace_aligned_to_128_bytes(env):
+    """The reference asserts a workspace aligned to 128 bytes (contraction.cu:242) and no more; the intermediate and both pairwise plans
+    ask for 128.  A workspace at 128 (mod 256) is accepted, and gives what a 256-aligned one gives, bit for bit."""
+    torch, ct, ops, h = env
+    ext = dict(a=24, b=20, c=64, d=18, e=30)
+    mA, mB, mC, mD = "acd", "cb", "de", "abe"
+    A, B, C, D = (make_tensor([ext[c] for c in m], 31 + i, np.float32) for i, m in enumerate((mA, mB, mC, mD)))
+    dA, dB, dC, dD = to_device(A), to_device(B), to_device(C), to_device(D)
+    plan = ops.contraction_trinary_plan(h, [ext[c] for c in mA], mA, [ext[c] for c in mB], mB, [ext[c] for c in mC], mC,
+                                        [ext[c] for c in mD], mD)
+    req = plan.required_workspace
+    buf = torch.empty(req + 512, dtype=torch.uint8, device="cuda")
+    base = (buf.data_ptr() + 255) // 256 * 256
+    outs = []
+    for ws in (base, base + 128):
+        out = torch.full_like(dD, float("nan"))
+        plan.contract_trinary(1.1, dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), 0.5, dD.data_ptr(), out.data_ptr(), ws, req)
+        torch.cuda.synchronize()
+        outs.append(out.cpu())
+    ref = 1.1 * np.einsum("acd,cb,de->abe", A.astype(np.float64), B.astype(np.float64), C.astype(np.float64)) + 0.5 * D
+    np.testing.assert_allclose(from_device(outs[1].cuda(), D), ref, rtol=1e-4)
+    assert torch.equal(outs[0], outs[1])
+    plan.destroy()
+
+
 def test_both_operands_permuted_single_pass(env):
     """A_{c,b,a} and B_{c,a,b} share the partner mode c of the output tile (elementwise_trinary.cu:51-53): one pass with
     two LDS tiles; must agree with the two-pass result bit for bit is not required (same operations, same order), but
