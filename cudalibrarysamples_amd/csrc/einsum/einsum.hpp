@@ -70,6 +70,9 @@ public:
     // conjugate an operand inside the contraction (python/einsum.h: the conjA / conjB arguments the PyTorch binding
     // uses for complex gradients, torch/einsum.py:50-61); call before plan() / execute()
     void setConjugate(bool conjA, bool conjB) { conjA_ = conjA; conjB_ = conjB; }
+    // compute descriptor of the contraction instead of the type trait's (e.g. CUTENSOR_COMPUTE_DESC_TF32 / _16BF / _16F on float data:
+    // products of rounded operands at the 16-bit matrix rate); call before plan().  nullptr = the trait's default.
+    void setComputeDescriptor(cutensorComputeDescriptor_t compute) { compute_ = compute; }
 
     Einsum(const std::string& equation, const std::vector<IntType>& A_shape,
            const std::vector<IntType>& B_shape = std::vector<IntType>()) {
@@ -147,7 +150,7 @@ public:
         if (!isInitialized_) return false;
         if (plan_) return true;
         const cutensorDataType_t type = EinsumTypeTraits<ComputeType>::dataType();
-        const cutensorComputeDescriptor_t compute = EinsumTypeTraits<ComputeType>::computeDesc();
+        const cutensorComputeDescriptor_t compute = compute_ ? compute_ : EinsumTypeTraits<ComputeType>::computeDesc();
         const uint32_t kAlignment = 128;
         cutensorTensorDescriptor_t dA = nullptr, dB = nullptr, dC = nullptr;
         cutensorOperationDescriptor_t op = nullptr;
@@ -213,6 +216,7 @@ private:
     bool isInitialized_ = false;
     bool hasB_ = false;
     bool conjA_ = false, conjB_ = false;
+    cutensorComputeDescriptor_t compute_ = nullptr;
     std::vector<int32_t> modesA_, modesB_, modesC_;
     std::vector<int64_t> extentA_, extentB_, extentC_;
     cutensorPlan_t plan_ = nullptr;

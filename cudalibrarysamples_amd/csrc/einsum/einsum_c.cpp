@@ -20,6 +20,7 @@ struct Base {
     virtual bool exec(cutensorHandle_t h, const void* A, const void* B, void* C, void* w, hipStream_t s) = 0;
     virtual cutensorPlan_t raw() const = 0;
     virtual void conj(bool a, bool b) = 0;
+    virtual void compute(cutensorComputeDescriptor_t c) = 0;
 };
 template <typename T>
 struct Impl : Base {
@@ -35,6 +36,7 @@ struct Impl : Base {
     }
     cutensorPlan_t raw() const override { return e.rawPlan(); }
     void conj(bool a, bool b) override { e.setConjugate(a, b); }
+    void compute(cutensorComputeDescriptor_t c) override { e.setComputeDescriptor(c); }
 };
 }  // namespace
 
@@ -55,6 +57,12 @@ void* ctamdEinsumCreate(const char* equation, const int64_t* shapeA, int nA, con
 } CTAMD_API_CATCH_NULL
 void ctamdEinsumDestroy(void* e) try { delete static_cast<Base*>(e); } CTAMD_API_CATCH_VOID
 void ctamdEinsumSetConjugate(void* e, int conjA, int conjB) try { if (e) static_cast<Base*>(e)->conj(conjA != 0, conjB != 0); } CTAMD_API_CATCH_VOID
+// compute descriptor by its index (0 16F, 1 16BF, 2 TF32, 3 3XTF32, 4 32F, 5 64F; anything else: the data type's default); before ctamdEinsumPlan
+void ctamdEinsumSetCompute(void* e, int id) try {
+    static const cutensorComputeDescriptor_t* const kDesc[6] = {&CUTENSOR_COMPUTE_DESC_16F, &CUTENSOR_COMPUTE_DESC_16BF, &CUTENSOR_COMPUTE_DESC_TF32,
+                                                                &CUTENSOR_COMPUTE_DESC_3XTF32, &CUTENSOR_COMPUTE_DESC_32F, &CUTENSOR_COMPUTE_DESC_64F};
+    if (e) static_cast<Base*>(e)->compute((id >= 0 && id < 6) ? *kDesc[id] : nullptr);
+} CTAMD_API_CATCH_VOID
 int ctamdEinsumIsInitialized(void* e) try { return e && static_cast<Base*>(e)->init() ? 1 : 0; } CTAMD_API_CATCH_INT
 int ctamdEinsumOutputShape(void* e, int64_t* out, int cap) try {
     if (!e) return -1;

@@ -154,7 +154,7 @@ bool plan_env_override() {
     return ctamd_research_env("CUTENSOR_AMD_FORCE") || ctamd_research_env("CUTENSOR_AMD_XCD_BALANCE") || CTAMD_HOOK_ENV("CUTENSOR_AMD_FUSED_FOLD") ||
            ctamd_research_env("CUTENSOR_AMD_H16_TRANSPOSE_T1") || CTAMD_HOOK_ENV("CUTENSOR_AMD_NT") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") || ctamd_research_env("CUTENSOR_AMD_H16_SPLITK") ||
            ctamd_research_env("CUTENSOR_AMD_KORDER") || ctamd_research_env("CUTENSOR_AMD_ABLATION") || CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") || CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") ||
-           CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY");
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X");
 }
 
 double scalar_as_double(const void* s, hipDataType t) {   // real part for complex scalar types
@@ -390,6 +390,58 @@ static double f64_direct_estimate_us(const ContractionView& v, const Contraction
 }
 // set while the inner contraction of a repacked plan is estimated / planned: the temporaries are final, no second round of copies
 static thread_local bool t_inRepack = false;
+
+// ---- reduced-precision compute descriptors on fp32 data (kernels/gett_gen_f32x.inc) -------------------------------------------
+// COMPUTE_DESC_16F / _16BF / _TF32 on a contraction whose tensors are all real fp32 with fp32 scalars PERMIT products of rounded
+// operands (fp16, bf16, three bf16 products of a hi / lo split); the fp32 kernels stay a legal answer.  Returns the general family's
+// element for the descriptor, or -1 when the contraction is not of that kind.
+static int f32x_elem_of(const cutensorOperationDescriptor& d) {
+    if (d.kind != OpKind::Contraction || d.compute == nullptr || d.scalarType != HIP_R_32F) return -1;
+    for (const TensorUse* t : {&d.A, &d.B, &d.C, &d.D})
+        if (t->present && t->desc.dtype != HIP_R_32F) return -1;
+    switch (d.compute->id) {
+        case 0:  return GEN_F32_F16;
+        case 1:  return GEN_F32_BF16;
+        case 2:  return GEN_F32_BF16X3;
+        default: return -1;
+    }
+}
+// CUTENSOR_AMD_F32X (test-hooks flavour): "force" — the reduced-precision kernels whenever the descriptor permits them; "0" — never
+static int f32x_switch() {
+    const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X");
+    return (e == nullptr) ? 0 : (e[0] == 'f') ? 1 : (e[0] == '0') ? -1 : 0;
+}
+// Whether a plan for view `v` (fp32 data, descriptor element `elem`) takes the reduced-precision kernels: `g` is their choice, `ch32` the
+// ranked fp32 candidates (best first).  By the model, only problems it can place: 16-byte loads on both operands, no split-K (the
+// headline einsum's class stays on the fp32 split-K kernels), at least one workgroup per CU, and an estimate clearly below the fp32
+// plan's.  `note` says which side won and on what numbers (the CUTENSOR_LOG_LEVEL plan line).
+static bool f32x_decide(const ContractionView& v, int elem, uint64_t wsLimit, int numCUs, bool explicitPick,
+                        const std::vector<ContractionChoice>& ch32, ContractionChoice& g, std::string& note) {
+    const int sw = f32x_switch();
+    char buf[256];
+    if (elem < 0 || v.wide || explicitPick || t_inRepack || sw < 0) return false;
+    if (!pick_gen_choice(v, wsLimit, numCUs, g, elem)) { note = "no reduced-precision kernel for this view -> fp32 kernels"; return false; }
+    const double t32 = (!ch32.empty() && ch32[0].family == 0 && ch32[0].kernel >= 0) ? ch32[0].estimateUs : -1.0;
+    if (sw > 0) {
+        std::snprintf(buf, sizeof buf, "reduced-precision kernels forced (model %.1f us, fp32 plan %.1f us)", g.estimateUs, t32);
+        note = buf;
+        return true;
+    }
+    int cnt = 0;
+    const GettKernelInfo* tab = gett_gen_kernels(&cnt);
+    const GettKernelInfo& k = tab[g.kernel];
+    const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
+    const char* why = nullptr;
+    if (t32 < 0.0) why = "no fp32 MFMA plan to compare with";
+    else if (k.vec != 4) why = "element gathers";
+    else if (g.splitK > 1 || ch32[0].splitK > 1) why = "split-K problem";
+    else if (tiles < (double)numCUs) why = "fewer output tiles than CUs";
+    else if (!(g.estimateUs < 0.8 * t32)) why = "model sees no gain";
+    std::snprintf(buf, sizeof buf, "%s (model: reduced-precision %.1f us, fp32 plan %.1f us)%s%s", why ? "fp32 kernels kept" : "reduced-precision kernels",
+                  g.estimateUs, t32, why ? ": " : "", why ? why : "");
+    note = buf;
+    return why == nullptr;
+}
 struct RepackScope { bool prev; RepackScope() : prev(t_inRepack) { t_inRepack = true; } ~RepackScope() { t_inRepack = prev; } };
 struct RepackSplit {
     cutensorOperationDescriptor inner, permA, permB;
@@ -1111,6 +1163,16 @@ cutensorStatus_t cutensorEstimateWorkspaceSize(const cutensorHandle_t handle, co
         if (v.dtype != HIP_R_32F) return CUTENSOR_STATUS_SUCCESS;
         // the largest workspace any of the best few candidates would like to have
         std::vector<ContractionChoice> ch = rank_contraction_choices(v, cap, handle->numCUs, planPref != nullptr && planPref->operandsStreamed != 0);
+        {   // reduced-precision compute descriptor: the same decision as cutensorCreatePlan — the split-K partials of that kernel
+            ContractionChoice gx;
+            std::string note;
+            const bool explicitPickX = planPref != nullptr && ((int)planPref->algo >= 0 || planPref->kernelRank > 0 || planPref->algo == CUTENSOR_ALGO_DEFAULT_PATIENT ||
+                                                               planPref->autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL);
+            if (f32x_decide(v, f32x_elem_of(*desc), cap, handle->numCUs, explicitPickX, ch, gx, note)) {
+                *workspaceSizeEstimate = gx.workspace;
+                return CUTENSOR_STATUS_SUCCESS;
+            }
+        }
         {
             RepackSplit rs;     // fp32 off the ring kernels: operands copied into packed temporaries first when that pays (plan_repack)
             const double tDirect = f32_direct_estimate_us(v, ch);
@@ -1198,7 +1260,7 @@ static int autotune_contraction(cutensorHandle_t handle, const cutensorOperation
                     // the fold that matches the kernel's partials: accumulator-register order (fp32 stream kernels), row-major fp32, or —
                     // general family with 8- / 16-byte elements — row-major partials in the accumulator type
                     const int elem = family == 2 ? tab[ch[i].kernel].elem : GEN_BF16;
-                    const hipError_t e = (family == 2 && elem >= GEN_F64) ? launch_gen_splitk_reduce(rp, elem, nullptr)
+                    const hipError_t e = (family == 2 && !gen_elem_f32_partials(elem)) ? launch_gen_splitk_reduce(rp, elem, nullptr)
                                        : tab[ch[i].kernel].fragPartials ? launch_splitk_reduce_frag(rp, nullptr) : launch_splitk_reduce(rp, nullptr);
                     if (e != hipSuccess) return false;
                 }
@@ -1562,6 +1624,19 @@ cutensorStatus_t cutensorCreatePlan(const cutensorHandle_t handle, cutensorPlan_
             ch = rank_h16_choices(pl->view, workspaceSizeLimit, handle->numCUs);
         double tDirect32 = (mfmaPath && desc->scalarType == HIP_R_32F && (int)pr.algo < 0 && pr.kernelRank == 0 && !ctamd_research_env("CUTENSOR_AMD_KORDER"))
                                ? f32_direct_estimate_us(pl->view, ch) : 0.0;
+        if (mfmaPath) {
+            // a reduced-precision compute descriptor: the bf16 / fp16-rate kernels when the model (or CUTENSOR_AMD_F32X=force) says so.
+            // They take the operands as they lie (no repack pre-pass); a caller who names a candidate addresses the fp32 list as ever.
+            const int xe = f32x_elem_of(*desc);
+            ContractionChoice gx;
+            std::string note;
+            const bool explicitPickX = (int)pr.algo >= 0 || pr.kernelRank > 0 || pr.algo == CUTENSOR_ALGO_DEFAULT_PATIENT || pr.autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL;
+            if (xe >= 0 && f32x_decide(pl->view, xe, workspaceSizeLimit, handle->numCUs, explicitPickX, ch, gx, note)) {
+                ch.assign(1, gx);
+                tDirect32 = 0.0;
+            }
+            if (xe >= 0 && !note.empty()) CT_LOG("plan: fp32 contraction, compute descriptor %s: %s", xe == GEN_F32_F16 ? "16F" : xe == GEN_F32_BF16 ? "16BF" : "TF32", note.c_str());
+        }
         if ((pl->view.dtype == HIP_R_64F || pl->view.dtype == HIP_C_32F) && desc->scalarType == pl->view.dtype && genPath && ch.empty()) {   // fp64 / complex64 on element gathers (plan_repack)
             ContractionChoice g64;
             if (pick_gen_choice(pl->view, workspaceSizeLimit, handle->numCUs, g64)) tDirect32 = f64_direct_estimate_us(pl->view, g64);
@@ -1993,7 +2068,7 @@ cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorP
             r.C = p.C; r.D = D; r.alpha = p.alpha; r.beta = p.beta;
             r.alpha64 = a; r.beta64 = b; r.alphaIm = aIm; r.betaIm = bIm; r.conjC = p.conjC;
             const int elem = plan->choice.family == 2 ? tab[plan->choice.kernel].elem : GEN_BF16;
-            err = (elem >= GEN_F64) ? launch_gen_splitk_reduce(r, elem, stream) : launch_splitk_reduce(r, stream);
+            err = !gen_elem_f32_partials(elem) ? launch_gen_splitk_reduce(r, elem, stream) : launch_splitk_reduce(r, stream);
         }
     } else {
         int count = 0;
@@ -2321,7 +2396,7 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
                           plan->gett.splitK, plan->gett.kPerSlice, plan->gett.nBlocks,
                           (unsigned long long)plan->requiredWorkspace, plan->choice.estimateUs, (int)plan->fusedFold,
                           (unsigned long long)plan->gett.xcdTiles,
-                          k == -2 ? "gett_wide_kernel" : k < 0 ? "gett_simple_kernel" : plan->choice.family == 2 ? "gett_gen_kernel" : plan->choice.family == 1 ? (tab[k].threads == 256 || tab[k].pf == 10 ? (tab[k].bk == 32 ? "gett_h16w4s_kernel" : tab[k].pf == 3 ? "gett_h16w4r_kernel" : tab[k].pf == 6 ? "gett_h16w4v_kernel" : tab[k].pf == 7 ? "gett_h16w4x_kernel" : tab[k].pf == 8 ? "gett_h16w4m_kernel" : tab[k].pf == 9 ? "gett_h16w4m4_kernel" : tab[k].pf == 10 ? "gett_h16w8m_kernel" : tab[k].pf == 11 ? "gett_h16w4q_kernel" : tab[k].pf == 12 ? "gett_h16w4p_kernel" : "gett_h16w4_kernel") : tab[k].pf == 4 ? "gett_h16s_kernel" : "gett_h16_kernel") : tab[k].fragPartials ? "gett_f32_stream_kernel" : "gett_f32_kernel");
+                          k == -2 ? "gett_wide_kernel" : k < 0 ? "gett_simple_kernel" : plan->choice.family == 2 ? (gen_elem_is_f32x(tab[k].elem) ? "gett_gen_f32x_kernel" : "gett_gen_kernel") : plan->choice.family == 1 ? (tab[k].threads == 256 || tab[k].pf == 10 ? (tab[k].bk == 32 ? "gett_h16w4s_kernel" : tab[k].pf == 3 ? "gett_h16w4r_kernel" : tab[k].pf == 6 ? "gett_h16w4v_kernel" : tab[k].pf == 7 ? "gett_h16w4x_kernel" : tab[k].pf == 8 ? "gett_h16w4m_kernel" : tab[k].pf == 9 ? "gett_h16w4m4_kernel" : tab[k].pf == 10 ? "gett_h16w8m_kernel" : tab[k].pf == 11 ? "gett_h16w4q_kernel" : tab[k].pf == 12 ? "gett_h16w4p_kernel" : "gett_h16w4_kernel") : tab[k].pf == 4 ? "gett_h16s_kernel" : "gett_h16_kernel") : tab[k].fragPartials ? "gett_f32_stream_kernel" : "gett_f32_kernel");
         // contracted digits, fastest first: [extent, strideA, strideB]
         if (n > 0 && (size_t)n < len && k >= 0)     // 1: the kernel streams its operands with the nontemporal policy (no Infinity-Cache allocation)
             n += std::snprintf(buf + n, len - n, ",\"nt\":%d", tab[k].nt);

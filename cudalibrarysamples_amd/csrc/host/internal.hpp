@@ -116,7 +116,7 @@ struct ContractionView {
 struct ContractionChoice {
     int      kernel = -1;      // index into the family's kernel table; -1 = simple kernel
     int      family = 0;       // 0 = gett_f32_kernels() (fp32 data), 1 = gett_h16_kernels() (bf16 / fp16 data, aligned shapes),
-                               // 2 = gett_gen_kernels() (general MFMA family: any 16-bit shape, fp64, complex)
+                               // 2 = gett_gen_kernels() (general MFMA family: any 16-bit shape, fp64, complex; fp32 data under a reduced-precision compute descriptor)
     uint32_t splitK = 1;
     uint32_t kPerSlice = 0;
     uint64_t workspace = 0;
@@ -136,7 +136,8 @@ std::vector<ContractionChoice> rank_contraction_choices(const ContractionView& v
                                                         int numCUs, bool operandsStreamed = false);
 bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c);
 // general MFMA family (kernels/gett_gen.inc): false only for fp32 data and for views the tiled kernels cannot describe
-bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c);
+// (f32xElem: fp32 data under a reduced-precision compute descriptor — GEN_F32_BF16 / GEN_F32_F16 / GEN_F32_BF16X3, gett_gen_f32x.inc)
+bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c, int f32xElem = -1);
 // 16-bit family: the default kernel variant first, then the other variants of the same tile / split (the candidates
 // CUTENSOR_ALGO_DEFAULT_PATIENT and incremental autotuning measure)
 std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64_t wsLimit, int numCUs);

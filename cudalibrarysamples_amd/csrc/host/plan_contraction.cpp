@@ -723,6 +723,9 @@ std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64
 // tiles alone leave most CUs idle: partials in the accumulator type — fp32 for 16-bit data (folded by launch_splitk_reduce with one
 // rounding), double / float2 / double2 otherwise (launch_gen_splitk_reduce).
 // ---------------------------------------------------------------------------------------------
+// efficiency of the reduced-precision fp32 kernels against their MFMA ceiling (one product per k-block / three): see pick_gen_choice
+static constexpr double kF32xEffX1 = 0.18, kF32xEffX3 = 0.275;
+
 static int gen_elem_of(hipDataType t) {
     switch (t) {
         case HIP_R_16BF: return GEN_BF16;
@@ -756,10 +759,12 @@ static int gen_operand_vec(const ContractionView& v, bool slotA, int orient, int
     return 1;
 }
 
-bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c) {
-    const int elem = gen_elem_of(v.dtype);
+bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c, int f32xElem) {
+    // fp32 data enters this family only under a reduced-precision compute descriptor (f32xElem: GEN_F32_BF16 / _F16 / _BF16X3)
+    const int elem = (v.dtype == HIP_R_32F) ? (gen_elem_is_f32x(f32xElem) ? f32xElem : -1) : gen_elem_of(v.dtype);
     if (elem < 0 || v.wide) return false;
-    const int maxV = (elem == GEN_C64) ? 1 : (elem == GEN_F64 || elem == GEN_C32) ? 2 : 8;
+    const bool f32x = gen_elem_is_f32x(elem);
+    const int maxV = (elem == GEN_C64) ? 1 : (elem == GEN_F64 || elem == GEN_C32) ? 2 : f32x ? 4 : 8;
     int orient[2], vec[2];
     for (int o = 0; o < 2; ++o) {
         const bool slotA = o == 0;
@@ -777,6 +782,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     }
     int V = std::min(vec[0], vec[1]);
     if (elem <= GEN_F16 && V == 4) V = 2;          // instantiated widths: 8 / 2 / 1 (16-bit), 2 / 1 (fp64, complex64), 1 (complex128)
+    if (f32x && V == 2) V = 1;                     // 4 / 1 (fp32 data, reduced-precision compute)
     int count = 0;
     const GettKernelInfo* tab = gett_gen_kernels(&count);
     // candidates of this (type, V, orientation pair): the table lists the larger tile first
@@ -798,7 +804,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     const uint64_t kTiles = (v.totK + k.bk - 1) / k.bk;
     // split-K when the output tiles alone leave most CUs idle: partial tiles [slice][L][M][N] in the accumulator type
     // (fp32 for 16-bit data, double / float2 / double2 for fp64 / complex64 / complex128)
-    const uint64_t accBytes = (elem <= GEN_F16) ? 4ull : (elem == GEN_C64) ? 16ull : 8ull;
+    const uint64_t accBytes = gen_elem_f32_partials(elem) ? 4ull : (elem == GEN_C64) ? 16ull : 8ull;
     const uint64_t perSliceBytes = v.totL * v.totM * v.totN * accBytes;
     // From 16 K-tiles on, slices of at least four.  (Round 4 raised this to 48 K-tiles on a misread pair of numbers; the records say the
     // opposite — the reference's fp16 case 'mlik,lkjm->lij', 50 batches x 32 K-tiles on 2-byte gathers: 19.2 us in five slices
@@ -818,9 +824,20 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     c.kPerSlice = (uint32_t)(tilesPerSlice * k.bk);
     c.workspace = (c.splitK > 1) ? (uint64_t)c.splitK * perSliceBytes : 0ull;
     // rough time: the family's MFMA rate for the type at ~50 % utilisation (only used for logs / describe)
-    const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32) ? 256.0 : 128.0;
-    const double flops = ((elem >= GEN_C32) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
+    const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32) ? 256.0 : f32x ? (elem == GEN_F32_BF16X3 ? 4096.0 / 3.0 : 4096.0) : 128.0;
+    const double flops = ((elem == GEN_C32 || elem == GEN_C64) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
     c.estimateUs = std::ceil(tiles * c.splitK / (double)numCUs) * flops / (flopPerClkCU * 2.4e9 * 0.5) * 1e6 + 2.0;
+    if (f32x) {
+        // The estimate that decides between these kernels and the ranked fp32 candidates (cutensorCreatePlan).  Waves of workgroups at
+        // the mode's MFMA rate times ONE efficiency factor per mode, fitted to the forced-path rows of the 4096^3 layouts in
+        // profiles/f32x_f32_compute.jsonl (DESIGN.md, section on the reduced-precision path); never below what moving the operands
+        // and the output once at 4 TB/s costs; launch 4 us.
+        const double eff = (elem == GEN_F32_BF16X3) ? kF32xEffX3 : kF32xEffX1;
+        const double slots = (double)numCUs * ((k.bm * k.bn <= 64 * 64) ? 2.0 : 1.0);
+        const double tCompute = std::ceil(tiles * c.splitK / slots) * ((k.bm * k.bn <= 64 * 64) ? 2.0 : 1.0) * flops / (flopPerClkCU * 2.4e9 * eff) * 1e6;
+        const double bytes = 4.0 * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
+        c.estimateUs = std::max(tCompute, bytes / 4.0e12 * 1e6) + 4.0;
+    }
     return true;
 }
 

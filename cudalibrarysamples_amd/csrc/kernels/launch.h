@@ -30,7 +30,13 @@ struct GettKernelInfo {
 };
 
 // element types of the general MFMA family (gett_gen.inc)
-enum GenElem : int { GEN_BF16 = 0, GEN_F16 = 1, GEN_F64 = 2, GEN_C32 = 3, GEN_C64 = 4 };
+enum GenElem : int { GEN_BF16 = 0, GEN_F16 = 1, GEN_F64 = 2, GEN_C32 = 3, GEN_C64 = 4,
+                     // fp32 DATA under a reduced-precision compute descriptor (gett_gen_f32x.inc): operands rounded to bf16 / fp16, or split
+                     // into two bf16 planes (three products: COMPUTE_DESC_TF32), on their way into LDS; fp32 accumulators, partials, epilogue
+                     GEN_F32_BF16 = 5, GEN_F32_F16 = 6, GEN_F32_BF16X3 = 7 };
+inline bool gen_elem_is_f32x(int elem) { return elem >= GEN_F32_BF16 && elem <= GEN_F32_BF16X3; }
+// split-K partials of the element type are fp32 rows folded by launch_splitk_reduce (else: launch_gen_splitk_reduce)
+inline bool gen_elem_f32_partials(int elem) { return elem == GEN_BF16 || elem == GEN_F16 || gen_elem_is_f32x(elem); }
 
 // fp32 data, fp32 MFMA (v_mfma_f32_16x16x4_f32)
 const GettKernelInfo* gett_f32_kernels(int* count);
@@ -46,11 +52,13 @@ const GettKernelInfo* gett_h16p_kernels(int* count);   // gett_h16p.hip (persist
 
 // general MFMA family: bf16 / fp16 shapes the aligned kernels above refuse (no 16-byte lanes, K not in whole 64-deep tiles), fp64,
 // complex64 / complex128 — register-staged, any strides and extents (gett_gen.inc; the table is the concatenation of the three
-// translation units gett_gen_h16.hip / gett_gen_f64.hip / gett_gen_cplx.hip)
+// translation units gett_gen_h16.hip / gett_gen_f64.hip / gett_gen_cplx.hip, then — appended, so that every earlier index stays — the
+// reduced-precision fp32 kernels of gett_gen_f32x.hip)
 const GettKernelInfo* gett_gen_kernels(int* count);
 const GettKernelInfo* gett_gen_h16_kernels(int* count);
 const GettKernelInfo* gett_gen_f64_kernels(int* count);
 const GettKernelInfo* gett_gen_cplx_kernels(int* count);
+const GettKernelInfo* gett_gen_f32x_kernels(int* count);
 // split-K fold of the general family's fp64 / complex kernels: D = alpha * sum_s partial[s] + beta * op(C); partials
 // [slice][L][M][N] in the accumulator type of `elem` (GEN_F64: double, GEN_C32: float2, GEN_C64: double2)
 hipError_t launch_gen_splitk_reduce(const SplitKReduceParams& p, int elem, hipStream_t stream);

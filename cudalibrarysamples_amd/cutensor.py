@@ -125,6 +125,8 @@ lib.ctamdEinsumCreate.argtypes = [ctypes.c_char_p, _i64p, ctypes.c_int, _i64p, c
 lib.ctamdEinsumCreate.restype = _vp
 lib.ctamdEinsumSetConjugate.argtypes = [_vp, ctypes.c_int, ctypes.c_int]
 lib.ctamdEinsumSetConjugate.restype = None
+lib.ctamdEinsumSetCompute.argtypes = [_vp, ctypes.c_int]
+lib.ctamdEinsumSetCompute.restype = None
 lib.ctamdEinsumDestroy.argtypes = [_vp]
 lib.ctamdEinsumDestroy.restype = None
 lib.ctamdEinsumIsInitialized.argtypes = [_vp]

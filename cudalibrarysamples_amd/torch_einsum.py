@@ -13,6 +13,12 @@ from . import cutensor as ct
 _TORCH2CT = {torch.float32: ct.R_32F, torch.float64: ct.R_64F, torch.float16: ct.R_16F, torch.bfloat16: ct.R_16BF,
              torch.complex64: ct.C_32F, torch.complex128: ct.C_64F}   # complex: contractions, and unary equations (reduce / permute)
 
+# compute= of EinsumPlan / einsum (float32 tensors): index of the compute descriptor (CUTENSOR_COMPUTE_DESC_<name>).  A reduced-precision
+# name permits products of rounded operands — "16BF": bf16(a) * bf16(b); "16F": fp16(a) * fp16(b) (beyond +-65504: +-inf); "TF32": three
+# bf16 products of a hi / lo split (about 2^-16 relative per product) — always with fp32 accumulation; the planner may still answer in
+# full fp32.  "32F" (= None) is the default.
+_COMPUTE = {"16F": 0, "16BF": 1, "TF32": 2, "32F": 4}
+
 _handle = None
 
 
@@ -30,13 +36,16 @@ def get_handle():
 class EinsumPlan:
     """Parsed + planned equation for fixed shapes/dtype (plan()/execute() split of python/einsum.h)."""
 
-    def __init__(self, equation, a_shape, b_shape, dtype, conj_a=False, conj_b=False):
+    def __init__(self, equation, a_shape, b_shape, dtype, conj_a=False, conj_b=False, compute=None):
+        compute = _check_compute(compute, dtype)
         self.e = ct.lib.ctamdEinsumCreate(equation.encode(), ct.i64(list(a_shape)), len(a_shape),
                                           ct.i64(list(b_shape)), len(b_shape), _TORCH2CT[dtype])
         if not self.e or not ct.lib.ctamdEinsumIsInitialized(self.e):
             raise ValueError("cutensor einsum: '%s' not supported for shapes %s, %s" % (equation, tuple(a_shape), tuple(b_shape)))
         if conj_a or conj_b:
             ct.lib.ctamdEinsumSetConjugate(self.e, int(conj_a), int(conj_b))
+        if compute is not None:
+            ct.lib.ctamdEinsumSetCompute(self.e, _COMPUTE[compute])
         out = (ctypes.c_int64 * 64)()
         n = ct.lib.ctamdEinsumOutputShape(self.e, out, 64)
         self.output_shape = [out[i] for i in range(n)]
@@ -72,21 +81,38 @@ class EinsumPlan:
             pass
 
 
+def _check_compute(compute, dtype):
+    """None or one of _COMPUTE's names; anything but the default (None, "32F") needs float32 tensors.  Returns None for the default."""
+    if compute is None:
+        return None
+    if compute not in _COMPUTE:
+        raise ValueError("cutensor einsum: compute must be one of None, %s" % ", ".join(repr(k) for k in _COMPUTE))
+    if compute == "32F":
+        return None
+    if dtype != torch.float32:
+        raise ValueError("cutensor einsum: compute=%r needs float32 tensors, got %s" % (compute, dtype))
+    return compute
+
+
 _plans = {}
 _workspace = {}
 
 
-def einsum(equation, a, b=None, conj_a=False, conj_b=False):
+def einsum(equation, a, b=None, conj_a=False, conj_b=False, compute=None):
     """out = einsum(equation, a[, b]) on the GPU holding `a`.  Inputs must be contiguous.  conj_a / conj_b conjugate an
-    operand inside the contraction (python/cutensor/torch/einsum.py:50-61 uses them for complex gradients)."""
+    operand inside the contraction (python/cutensor/torch/einsum.py:50-61 uses them for complex gradients).  compute (float32
+    tensors only): None / "32F", or "TF32" / "16BF" / "16F" to permit reduced-precision products (see _COMPUTE)."""
+    compute = _check_compute(compute, a.dtype)
     if not a.is_cuda:
         raise RuntimeError("cutensor einsum runs on the GPU only (there is no CPU path)")
     a = a.contiguous()
     b = b.contiguous() if b is not None else None
     key = (equation, tuple(a.shape), tuple(b.shape) if b is not None else (), a.dtype, bool(conj_a), bool(conj_b))
+    if compute is not None:
+        key += (compute,)          # (the default keeps the key it always had)
     plan = _plans.get(key)
     if plan is None:
-        plan = _plans[key] = EinsumPlan(equation, a.shape, b.shape if b is not None else (), a.dtype, conj_a, conj_b)
+        plan = _plans[key] = EinsumPlan(equation, a.shape, b.shape if b is not None else (), a.dtype, conj_a, conj_b, compute)
     out = torch.empty(plan.output_shape, dtype=a.dtype, device=a.device)
     try:
         ws = _get_workspace(a.device, plan.required_workspace)
