@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <sstream>
 
 #include <hip/hip_runtime.h>
@@ -170,6 +171,29 @@ double scalar_imag(const void* s, hipDataType t) {
 
 bool misaligned(const void* p, uint32_t a) { return a > 1 && (reinterpret_cast<uintptr_t>(p) % a) != 0; }
 
+// pieces of the workspace start at multiples of 256 bytes
+constexpr uint64_t align256(uint64_t bytes) { return (bytes + 255) & ~255ull; }
+// Two-step plans (PlanKind::LoneReduce / Repack) and their estimate: A's temporary at the head of the workspace, B's at offB, the
+// sub-plans' own workspace from offW on
+struct TwoStepLayout {
+    const uint64_t offB, offW;
+    TwoStepLayout(uint64_t bytesA, uint64_t bytesB) : offB(align256(bytesA)), offW(offB + align256(bytesB)) {}
+};
+
+// the caller names a candidate of the ranked list (CUTENSOR_ALGO >= 0 or a kernel rank): it gets that candidate
+bool names_candidate(const cutensorPlanPreference& pr) { return (int)pr.algo >= 0 || pr.kernelRank > 0; }
+// ... or asks for a measured choice among the candidates (CUTENSOR_ALGO_DEFAULT_PATIENT, incremental autotuning)
+bool names_candidate_or_tunes(const cutensorPlanPreference& pr) { return names_candidate(pr) || pr.algo == CUTENSOR_ALGO_DEFAULT_PATIENT || pr.autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL; }
+
+// the kernel table a ContractionChoice::kernel of `family` indexes
+const GettKernelInfo* kernel_table(int family, int* count) { return family == 2 ? gett_gen_kernels(count) : family == 1 ? gett_h16_kernels(count) : gett_f32_kernels(count); }
+// ... and the entry itself; nullptr when `kernel` is not an index into that table
+const GettKernelInfo* kernel_info(int family, int kernel) {
+    int n = 0;
+    const GettKernelInfo* tab = kernel_table(family, &n);
+    return (kernel >= 0 && kernel < n) ? &tab[kernel] : nullptr;
+}
+
 }  // namespace
 
 // Incremental autotuning (contraction_plan_cache.cu:215-237): cutensorContract on a trial plan brackets its launches with
@@ -201,35 +225,26 @@ static void resolve_pending_measurements(cutensorHandle* handle) {
     }
 }
 
-// A finished plan that owns nothing becomes the prototype later plans of the same problem are cloned from; the least
+// A finished plan of the kinds plan_is_prototype lists becomes the prototype later plans of the same problem are cloned from; the least
 // recently used prototype makes room when the cache is full (capacity = cutensorHandleResizePlanCache's numEntries).
-// A plan holds device memory, a trial's timing state or a block-sparse task list of its own: nothing a copy may share
-static bool plan_is_plain(const cutensorPlan& pl) {
-    return pl.tuneKey.empty() && pl.wide.modes == nullptr && pl.wideTab.empty() && !pl.bsp;
-}
-// Copy of a plan; the plans of a two-step contraction (choice.kernel == -4: an operand reduced over its lone modes or copied into a packed
-// temporary first, then the inner contraction) are copied with it — every one of them plain (round 6: such plans are memoised too; the
-// planner prices up to eight copy combinations for them, 100-240 us per cutensorCreatePlan, and einsum.cu plans inside every call)
-static cutensorPlan* clone_plan(const cutensorPlan& src) {
-    cutensorPlan* c = new (std::nothrow) cutensorPlan(src);
-    if (c == nullptr) return nullptr;
-    c->sub1 = c->sub2 = c->loneA = c->loneB = nullptr;
-    const cutensorPlan* from[4] = {src.sub1, src.sub2, src.loneA, src.loneB};
-    cutensorPlan** to[4] = {&c->sub1, &c->sub2, &c->loneA, &c->loneB};
-    for (int i = 0; i < 4; ++i)
-        if (from[i] != nullptr && (*to[i] = clone_plan(*from[i])) == nullptr) { delete c; return nullptr; }
-    return c;
-}
+// A mode table, a trial's timing state or a block-sparse task list: such plans are planned every time
+static bool plan_is_plain(const cutensorPlan& pl) { return pl.tuneKey.empty() && pl.wideTab.empty() && !pl.bsp; }
+static bool plan_has_sub_plans(const cutensorPlan& pl) { return pl.sub1 || pl.sub2 || pl.loneA || pl.loneB; }
+// Copy of a plan (it shares the source's sub-plans: SubPlan, internal.hpp)
+static cutensorPlan* clone_plan(const cutensorPlan& src) { return new (std::nothrow) cutensorPlan(src); }
+// What the memo holds: plain plans without sub-plans, and two-step contractions (an operand reduced over its lone modes or copied into a
+// packed temporary first, then the inner contraction) whose plans are all of that kind (round 6: the planner prices up to eight copy
+// combinations for them, 100-240 us per cutensorCreatePlan, and einsum.cu plans inside every call).  Peeled / trinary plans: not memoised
 static bool plan_is_prototype(const cutensorPlan& pl) {
     if (!plan_is_plain(pl)) return false;
-    if (pl.sub1 == nullptr && pl.sub2 == nullptr && pl.loneA == nullptr && pl.loneB == nullptr) return true;
-    if (pl.kind != OpKind::Contraction || pl.choice.kernel != -4 || pl.sub2 != nullptr || pl.sub1 == nullptr) return false;   // (peeled / trinary plans: not memoised)
-    for (const cutensorPlan* q : {static_cast<const cutensorPlan*>(pl.sub1), static_cast<const cutensorPlan*>(pl.loneA), static_cast<const cutensorPlan*>(pl.loneB)})
-        if (q != nullptr && (!plan_is_plain(*q) || q->sub1 || q->sub2 || q->loneA || q->loneB)) return false;
+    if (!plan_has_sub_plans(pl)) return true;
+    if (pl.kind != OpKind::Contraction || (pl.planKind != PlanKind::LoneReduce && pl.planKind != PlanKind::Repack) || pl.sub2 || !pl.sub1) return false;
+    for (const SubPlan* q : {&pl.sub1, &pl.loneA, &pl.loneB})
+        if (*q && (!plan_is_plain(**q) || plan_has_sub_plans(**q))) return false;
     return true;
 }
 static void memo_insert(cutensorHandle* h, const PlanMemoKey& key, uint64_t hash, const cutensorPlan& pl) {
-    if (!plan_is_prototype(pl)) return;   // plans that own something are not prototypes
+    if (!plan_is_prototype(pl)) return;
     std::shared_ptr<const cutensorPlan> proto(clone_plan(pl));
     if (!proto) return;
     std::lock_guard<std::mutex> g(h->mtx);
@@ -300,13 +315,26 @@ static bool peel_wide_contraction(const cutensorOperationDescriptor& desc, cuten
 // then the ordinary contraction runs on the temporary.  (Summing first is also the cheap order: the contraction shrinks by the mode's
 // extent.)  Returns false when the descriptor has no such mode; fills `inner` (the contraction on the temporaries) and the
 // reductions otherwise.
-struct LoneSplit {
-    cutensorOperationDescriptor inner, redA, redB;
+// (split_lone_modes and plan_repack: the first steps — reductions or permuted copies of A / B — and the contraction on their results)
+struct TwoStepSplit {
+    cutensorOperationDescriptor inner, stepA, stepB;
     bool hasA = false, hasB = false;
     uint64_t bytesA = 0, bytesB = 0;       // packed sizes of the temporaries
-    int64_t summedA = 1, summedB = 1;      // elements summed into each element of a temporary
+    int64_t summedA = 1, summedB = 1;      // lone modes: elements summed into each element of a temporary
 };
-static bool split_lone_modes(const cutensorOperationDescriptor& desc, LoneSplit& out) {
+// the packed temporary an operand X is reduced or copied into: a piece of the workspace at a multiple of 256 bytes, as aligned as the
+// workspace itself (contraction.cu:242 asserts 128); its modes are pushed fastest first
+struct PackedTemporary {
+    TensorUse use;
+    int64_t   elems = 1;
+    explicit PackedTemporary(const TensorUse& X) { use.present = true; use.op = X.op; use.desc.dtype = X.desc.dtype; use.desc.alignment = 128; }
+    void push(int32_t label, int64_t extent) {
+        use.modes.push_back(label); use.desc.extent.push_back(extent); use.desc.stride.push_back(elems);
+        use.desc.numModes += 1; elems *= extent;
+    }
+    uint64_t bytes() const { return (uint64_t)elems * dtype_size(use.desc.dtype); }
+};
+static bool split_lone_modes(const cutensorOperationDescriptor& desc, TwoStepSplit& out) {
     auto has = [](const std::vector<int32_t>& v, int32_t l) { return std::find(v.begin(), v.end(), l) != v.end(); };
     auto reduce_operand = [&](const TensorUse& X, const TensorUse& other, cutensorOperationDescriptor& red, TensorUse& kept, uint64_t& bytes,
                               int64_t& summed) {
@@ -314,22 +342,14 @@ static bool split_lone_modes(const cutensorOperationDescriptor& desc, LoneSplit&
         for (size_t i = 0; i < X.modes.size(); ++i)
             if (X.desc.extent[i] != 1 && !has(other.modes, X.modes[i]) && !has(desc.C.modes, X.modes[i])) lone = true;
         if (!lone) return false;
-        kept = TensorUse{};
-        kept.present = true;
-        kept.op = X.op;                                         // conj(sum) = sum(conj): the inner contraction conjugates
-        kept.desc.dtype = X.desc.dtype;
-        kept.desc.alignment = 128;                              // a piece of the workspace at a multiple of 256 bytes: as aligned as the workspace itself (contraction.cu:242 asserts 128)
-        int64_t run = 1;
+        PackedTemporary t(X);                                   // (it keeps X's operator: conj(sum) = sum(conj), the inner contraction conjugates)
         summed = 1;
         for (size_t i = 0; i < X.modes.size(); ++i) {
-            if (!has(other.modes, X.modes[i]) && !has(desc.C.modes, X.modes[i])) { summed *= X.desc.extent[i]; continue; }   // summed away (extent-1 lone modes too)
-            kept.modes.push_back(X.modes[i]);
-            kept.desc.extent.push_back(X.desc.extent[i]);
-            kept.desc.stride.push_back(run);
-            run *= X.desc.extent[i];
+            if (!has(other.modes, X.modes[i]) && !has(desc.C.modes, X.modes[i])) summed *= X.desc.extent[i];   // summed away (extent-1 lone modes too)
+            else t.push(X.modes[i], X.desc.extent[i]);
         }
-        kept.desc.numModes = (uint32_t)kept.modes.size();
-        bytes = (uint64_t)run * dtype_size(X.desc.dtype);
+        kept = t.use;
+        bytes = t.bytes();
         red = cutensorOperationDescriptor{};
         red.kind = OpKind::Reduction;
         red.A = X;
@@ -342,8 +362,8 @@ static bool split_lone_modes(const cutensorOperationDescriptor& desc, LoneSplit&
         return true;
     };
     TensorUse keptA, keptB;
-    out.hasA = reduce_operand(desc.A, desc.B, out.redA, keptA, out.bytesA, out.summedA);
-    out.hasB = reduce_operand(desc.B, desc.A, out.redB, keptB, out.bytesB, out.summedB);
+    out.hasA = reduce_operand(desc.A, desc.B, out.stepA, keptA, out.bytesA, out.summedA);
+    out.hasB = reduce_operand(desc.B, desc.A, out.stepB, keptB, out.bytesB, out.summedB);
     if (!out.hasA && !out.hasB) return false;
     out.inner = desc;
     if (out.hasA) out.inner.A = keptA;
@@ -371,20 +391,18 @@ static bool h16_sweep_waste(const ContractionView& v) {
 // profiles/r06zzb_sweep_shapes_f32.jsonl: x 1.15 with 16-byte lanes (422 / 2103 / 170 us modelled, 498 / 2333 / 204 measured), x 2.5 when an
 // operand is gathered element by element (390 / 265 / 1346 modelled, 1064 / 552 / 5865 measured)
 static double f32_direct_estimate_us(const ContractionView& v, const std::vector<ContractionChoice>& ch) {
-    if (v.dtype != HIP_R_32F || v.wide || ch.empty() || ch[0].family != 0 || ch[0].kernel < 0) return 0.0;
-    int cnt = 0;
-    const GettKernelInfo* t32 = gett_f32_kernels(&cnt);
-    if (ch[0].kernel >= cnt || t32[ch[0].kernel].fragPartials) return 0.0;
+    if (v.dtype != HIP_R_32F || v.wide || ch.empty() || ch[0].family != 0) return 0.0;
+    const GettKernelInfo* k = kernel_info(0, ch[0].kernel);
+    if (k == nullptr || k->fragPartials) return 0.0;
     return ch[0].estimateUs * ((v.layA == LAY_S || v.layB == LAY_S) ? 2.5 : 1.15);
 }
 // fp64: what the general family costs when the direct plan gathers single elements (V = 1: 'ijk,lkj->il' 30 TFLOP/s, the larger 'mlik' case
 // 15 — profiles/r06zzi_sweep_shapes_f64.jsonl); 0 when it stages 16-byte units (nothing to gain from a copy)
 // complex64 likewise (8 real flops per multiply-add): 103 / 58 TFLOP/s on those two shapes at V = 1 (profiles/r06zzm_sweep_shapes_c64_before.jsonl)
 static double f64_direct_estimate_us(const ContractionView& v, const ContractionChoice& gc) {
-    if ((v.dtype != HIP_R_64F && v.dtype != HIP_C_32F) || v.wide || gc.family != 2 || gc.kernel < 0) return 0.0;
-    int cnt = 0;
-    const GettKernelInfo* tg = gett_gen_kernels(&cnt);
-    if (gc.kernel >= cnt || tg[gc.kernel].vec >= 2) return 0.0;
+    if ((v.dtype != HIP_R_64F && v.dtype != HIP_C_32F) || v.wide || gc.family != 2) return 0.0;
+    const GettKernelInfo* k = kernel_info(2, gc.kernel);
+    if (k == nullptr || k->vec >= 2) return 0.0;
     const double mnk = (double)v.totL * (double)v.totM * (double)v.totN * (double)v.totK;
     return (v.dtype == HIP_C_32F ? 8.0 * mnk / 75e12 : 2.0 * mnk / 22e12) * 1e6 + 8.0;
 }
@@ -427,9 +445,7 @@ static bool f32x_decide(const ContractionView& v, int elem, uint64_t wsLimit, in
         note = buf;
         return true;
     }
-    int cnt = 0;
-    const GettKernelInfo* tab = gett_gen_kernels(&cnt);
-    const GettKernelInfo& k = tab[g.kernel];
+    const GettKernelInfo& k = *kernel_info(2, g.kernel);
     const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
     const char* why = nullptr;
     if (t32 < 0.0) why = "no fp32 MFMA plan to compare with";
@@ -443,14 +459,9 @@ static bool f32x_decide(const ContractionView& v, int elem, uint64_t wsLimit, in
     return why == nullptr;
 }
 struct RepackScope { bool prev; RepackScope() : prev(t_inRepack) { t_inRepack = true; } ~RepackScope() { t_inRepack = prev; } };
-struct RepackSplit {
-    cutensorOperationDescriptor inner, permA, permB;
-    bool hasA = false, hasB = false;
-    uint64_t bytesA = 0, bytesB = 0;       // packed sizes of the temporaries
-};
 // tDirectUs: the estimate of the plan that takes the operands as they lie, when the LDS-DMA family has one (sweeps of a short ragged contracted
 // mode waste most of every K-tile: 'abcd,dcbe->ae' with d = 16 keeps 16 of 64 k) — negative: the general family's model above.
-static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDescriptor& desc, const ContractionView& v, uint64_t wsLimit, double tDirectUs, RepackSplit& out) {
+static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDescriptor& desc, const ContractionView& v, uint64_t wsLimit, double tDirectUs, TwoStepSplit& out) {
     const bool f32 = v.dtype == HIP_R_32F, c32 = v.dtype == HIP_C_32F, f64 = v.dtype == HIP_R_64F || c32;   // (f64: the general family's wide elements)
     if (t_inRepack || v.wide || (v.dtype != HIP_R_16BF && v.dtype != HIP_R_16F && !f32 && !f64) || v.K.empty()) return false;
     const double es = (double)dtype_size(v.dtype);
@@ -473,13 +484,8 @@ static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDes
             if (inO && !inD) k.push_back(Km{l, X.desc.extent[i], std::llabs(freeMajor ? X.desc.stride[i] : stride_of(other, l))});
         }
         std::stable_sort(k.begin(), k.end(), [](const Km& a, const Km& b) { return a.so < b.so; });
-        kept = TensorUse{};
-        kept.present = true;
-        kept.op = X.op;
-        kept.desc.dtype = X.desc.dtype;
-        kept.desc.alignment = 128;                                          // (the workspace's own alignment, contraction.cu:242; the pieces start at multiples of 256 bytes)
-        int64_t run = 1;
-        auto push = [&](int32_t l, int64_t e) { kept.modes.push_back(l); kept.desc.extent.push_back(e); kept.desc.stride.push_back(run); run *= e; };
+        PackedTemporary t(X);
+        auto push = [&](int32_t l, int64_t e) { t.push(l, e); };
         if (!freeMajor) for (const Km& m : k) push(m.label, m.extent);
         for (int pass = 0; pass < 2; ++pass) {                              // free modes in D's order, then the batch modes
             if (freeMajor && pass == 1) for (const Km& m : k) push(m.label, m.extent);
@@ -488,9 +494,9 @@ static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDes
                 for (size_t i = 0; i < X.modes.size(); ++i) if (X.modes[i] == l) push(l, X.desc.extent[i]);
             }
         }
-        if (kept.modes.size() != X.modes.size()) return false;
-        kept.desc.numModes = (uint32_t)kept.modes.size();
-        bytes = (uint64_t)run * dtype_size(X.desc.dtype);
+        if (t.use.modes.size() != X.modes.size()) return false;
+        kept = t.use;
+        bytes = t.bytes();
         perm = cutensorOperationDescriptor{};
         perm.kind = OpKind::Permutation;
         perm.A = X;
@@ -503,7 +509,7 @@ static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDes
         // 13 MB of bf16 from [d = 50, c, b, a] to [b, c, d, a] in 380 us)
         EwPlan ep;
         if (plan_elementwise(perm, ep, nullptr) != CUTENSOR_STATUS_SUCCESS) return false;
-        const double elems = (double)run;
+        const double elems = (double)t.elems;
         if (ep.variant == EW_TRANSPOSE) {
             // (rows of a tile past the end of a mode are skipped, not moved: the padding costs about a third of live data — 'jkl -> kjl'
             // with 16 x 72 of every 64 x 128 tile pair live, 9.4 MB, measured ~15 us)
@@ -522,24 +528,24 @@ static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDes
     // order of the contracted modes, which then fuse into a single one (nothing ragged but the end of K).  The fastest one by the model,
     // if it beats the direct plan by a fifth.
     // (CUTENSOR_AMD_REPACK=f, hooks flavour: whenever the temporaries fit — the fuzzers' and the small parity cases' way onto this path)
-    const bool forced = CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") && CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK")[0] == 'f';
+    const bool forced = CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_REPACK", 'f');
     double best = 1e30;
     for (int attempt = 1; attempt < 9; ++attempt) {                         // per operand: 0 = as it lies, 1 = contracted modes fastest, 2 = free modes fastest
         const int howA = attempt % 3, howB = attempt / 3;
         const bool doA = howA != 0, doB = howB != 0;
         // (every combination is tried: an operand the kernels cannot stage as it lies may become stageable once the OTHER one is copied —
         // A[d = 50, c, b, a] is K-contiguous in the fused mode (d, c, b) as soon as B holds the contracted modes in that order)
-        RepackSplit r;
+        TwoStepSplit r;
         TensorUse keptA, keptB;
         // the order of the contracted modes follows the OTHER operand as it will be contracted: with both repacked, B follows A's temporary
         double usA = 0.0, usB = 0.0;
-        if (doA && !pack(desc.A, desc.B, howA == 2, r.permA, keptA, r.bytesA, usA)) continue;
-        if (doB && !pack(desc.B, doA ? keptA : desc.A, howB == 2, r.permB, keptB, r.bytesB, usB)) continue;
+        if (doA && !pack(desc.A, desc.B, howA == 2, r.stepA, keptA, r.bytesA, usA)) continue;
+        if (doB && !pack(desc.B, doA ? keptA : desc.A, howB == 2, r.stepB, keptB, r.bytesB, usB)) continue;
         r.hasA = doA; r.hasB = doB;
         r.inner = desc;
         if (doA) r.inner.A = keptA;
         if (doB) r.inner.B = keptB;
-        const uint64_t temps = ((r.bytesA + 255) & ~255ull) + ((r.bytesB + 255) & ~255ull);
+        const uint64_t temps = TwoStepLayout(r.bytesA, r.bytesB).offW;
         if (temps > wsLimit) continue;
         ContractionView vi;
         ContractionChoice hc;
@@ -547,17 +553,15 @@ static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDes
         if (f64) {
             // fp64 (general MFMA family, gett_gen.inc): the temporaries must give both operands 16-byte units (V = 2) where the direct plan
             // gathers single elements; the family's rates on the shapes of profiles/r06zzi_sweep_shapes_f64.jsonl: 52-59 TFLOP/s at V = 2
-            int cnt = 0;
-            const GettKernelInfo* tg = gett_gen_kernels(&cnt);
-            if (!pick_gen_choice(vi, wsLimit - temps, handle->numCUs, hc) || hc.kernel < 0 || hc.kernel >= cnt || tg[hc.kernel].vec < 2) continue;
+            const GettKernelInfo* k = pick_gen_choice(vi, wsLimit - temps, handle->numCUs, hc) ? kernel_info(2, hc.kernel) : nullptr;
+            if (k == nullptr || k->vec < 2) continue;
             hc.estimateUs = (c32 ? 4.0 * flops / 124e12 : flops / 55e12) * 1e6 + 8.0;   // (complex64 at V = 2: 124 TFLOP/s of real flops, r06zzm)
         } else if (f32) {
             // fp32: the temporaries must put the problem on the LDS-DMA ring kernels (gett_f32_stream.hip: whole 32-deep K-tiles in the
             // fastest contracted mode, or one ragged contracted mode)
             const std::vector<ContractionChoice> ci = rank_contraction_choices(vi, wsLimit - temps, handle->numCUs, false);
-            int cnt = 0;
-            const GettKernelInfo* t32 = gett_f32_kernels(&cnt);
-            if (ci.empty() || ci[0].family != 0 || ci[0].kernel < 0 || ci[0].kernel >= cnt || (!forced && !t32[ci[0].kernel].fragPartials)) continue;
+            const GettKernelInfo* k = (ci.empty() || ci[0].family != 0) ? nullptr : kernel_info(0, ci[0].kernel);
+            if (k == nullptr || (!forced && !k->fragPartials)) continue;
             hc = ci[0];
         } else if (!pick_h16_choice(vi, wsLimit - temps, handle->numCUs, hc)) continue;
         const double tCopies = usA + usB;
@@ -758,11 +762,11 @@ cutensorStatus_t cutensorCreateContraction(const cutensorHandle_t handle, cutens
     ContractionView v;
     std::string why;
     {
-        LoneSplit ls;     // a mode only one input carries: validated as the reduction(s) + the contraction on the temporaries (split_lone_modes)
+        TwoStepSplit ls;     // a mode only one input carries: validated as the reduction(s) + the contraction on the temporaries (split_lone_modes)
         if (split_lone_modes(op, ls)) {
             ReducePlan rp;
-            if (ls.hasA && (st = plan_reduction(ls.redA, 0, handle->numCUs, rp, &why)) != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
-            if (ls.hasB && (st = plan_reduction(ls.redB, 0, handle->numCUs, rp, &why)) != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
+            if (ls.hasA && (st = plan_reduction(ls.stepA, 0, handle->numCUs, rp, &why)) != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
+            if (ls.hasB && (st = plan_reduction(ls.stepB, 0, handle->numCUs, rp, &why)) != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
             st = build_contraction_view(ls.inner, v, &why);
             if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
             op.flops = 2.0 * (double)v.totL * (double)v.totM * (double)v.totN * (double)v.totK + (ls.hasA ? num_elements(op.A.desc) : 0.0) +
@@ -1080,123 +1084,145 @@ cutensorStatus_t cutensorPlanPreferenceSetAttribute(const cutensorHandle_t handl
     return CUTENSOR_STATUS_SUCCESS;
 } CTAMD_API_CATCH
 
+// what a repacked plan wants: the temporaries + what the inner contraction on them wants
+static cutensorStatus_t estimate_repacked(const cutensorHandle_t handle, TwoStepSplit& rs, const cutensorPlanPreference_t planPref,
+                                          const cutensorWorksizePreference_t workspacePref, uint64_t* estimate) {
+    uint64_t wI = 0;
+    RepackScope scope;
+    const cutensorStatus_t st = cutensorEstimateWorkspaceSize(handle, &rs.inner, planPref, workspacePref, &wI);
+    if (st == CUTENSOR_STATUS_SUCCESS) *estimate = TwoStepLayout(rs.bytesA, rs.bytesB).offW + wI;
+    return st;
+}
+
+// Contractions the tiled kernels can describe and the peeled ones, under the workspace cap of the preference: the same split / peel /
+// repack entry points as the plan builders (build_contraction), priced without building plans
+static cutensorStatus_t estimate_contraction(const cutensorHandle_t handle, cutensorOperationDescriptor& desc, const cutensorPlanPreference_t planPref,
+                                             const cutensorWorksizePreference_t workspacePref, uint64_t cap, uint64_t* estimate) {
+    ContractionView v;
+    const cutensorStatus_t st = build_contraction_view(desc, v, nullptr);
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    const int numCUs = handle->numCUs;
+    const bool acc64 = desc.compute && desc.compute->id == 5;
+    TwoStepSplit rs;
+    if (v.wide) {    // a peeled contraction wants what its inner, tiled problem wants
+        cutensorOperationDescriptor inner;
+        std::vector<PeelMode> peel;
+        if (!peel_wide_contraction(desc, inner, peel)) return CUTENSOR_STATUS_SUCCESS;
+        peel_fix_alignment(inner, peel);
+        return cutensorEstimateWorkspaceSize(handle, &inner, planPref, workspacePref, estimate);
+    }
+    if (v.dtype == HIP_R_16BF || v.dtype == HIP_R_16F) {   // split-K partials of the 16-bit MFMA kernel
+        ContractionChoice hc;
+        const bool direct = pick_h16_choice(v, cap, numCUs, hc);
+        const bool h16ok = desc.scalarType == HIP_R_32F && !acc64;
+        if (direct && !(h16ok && h16_sweep_waste(v))) *estimate = hc.workspace;
+        else if (h16ok && plan_repack(handle, desc, v, cap, direct ? hc.estimateUs : -1.0, rs)) return estimate_repacked(handle, rs, planPref, workspacePref, estimate);
+        else if (direct || pick_gen_choice(v, cap, numCUs, hc)) *estimate = hc.workspace;
+        return CUTENSOR_STATUS_SUCCESS;
+    }
+    if (v.dtype == HIP_R_64F || v.dtype == HIP_C_32F || v.dtype == HIP_C_64F) {   // split-K partials of the general MFMA family
+        ContractionChoice gc;
+        if (!pick_gen_choice(v, cap, numCUs, gc)) return CUTENSOR_STATUS_SUCCESS;
+        *estimate = gc.workspace;
+        // fp64 on element gathers: an operand copied first when that pays (plan_repack)
+        const double tDirect = desc.scalarType == v.dtype ? f64_direct_estimate_us(v, gc) : 0.0;
+        if (tDirect > 0.0 && plan_repack(handle, desc, v, cap, tDirect, rs)) return estimate_repacked(handle, rs, planPref, workspacePref, estimate);
+        return CUTENSOR_STATUS_SUCCESS;
+    }
+    if (v.dtype != HIP_R_32F) return CUTENSOR_STATUS_SUCCESS;
+    const std::vector<ContractionChoice> ch = rank_contraction_choices(v, cap, numCUs, planPref != nullptr && planPref->operandsStreamed != 0);
+    // reduced-precision compute descriptor: the same decision as rank_tiled_candidates — the split-K partials of that kernel
+    ContractionChoice gx;
+    std::string note;
+    if (f32x_decide(v, f32x_elem_of(desc), cap, numCUs, planPref != nullptr && names_candidate_or_tunes(*planPref), ch, gx, note)) {
+        *estimate = gx.workspace;
+        return CUTENSOR_STATUS_SUCCESS;
+    }
+    // fp32 off the ring kernels: operands copied into packed temporaries first when that pays (plan_repack)
+    const double tDirect = f32_direct_estimate_us(v, ch);
+    if (tDirect > 0.0 && !acc64 && desc.scalarType == HIP_R_32F && plan_repack(handle, desc, v, cap, tDirect, rs))
+        return estimate_repacked(handle, rs, planPref, workspacePref, estimate);
+    // the largest workspace any of the best few candidates would like to have
+    for (size_t i = 0; i < ch.size() && i < 4; ++i) *estimate = std::max(*estimate, ch[i].workspace);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+
 // contraction.cu:207-211
 cutensorStatus_t cutensorEstimateWorkspaceSize(const cutensorHandle_t handle, const cutensorOperationDescriptor_t desc,
                                                const cutensorPlanPreference_t planPref,
                                                const cutensorWorksizePreference_t workspacePref,
                                                uint64_t* workspaceSizeEstimate) try {
-    (void)planPref;
     if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
     if (desc == nullptr || workspaceSizeEstimate == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
     *workspaceSizeEstimate = 0;
+    auto estimate = [&](cutensorOperationDescriptor& d, uint64_t& w) { return cutensorEstimateWorkspaceSize(handle, &d, planPref, workspacePref, &w); };
     if (desc->kind == OpKind::BlockSparseContraction) return blocksparse_estimate(handle, *desc, workspaceSizeEstimate);
     if (desc->kind == OpKind::ContractionTrinary) {   // intermediate + the larger of the two pairwise needs
         uint64_t w1 = 0, w2 = 0;
         cutensorOperationDescriptor s1 = desc->sub[0], s2 = desc->sub[1];
-        cutensorStatus_t st = cutensorEstimateWorkspaceSize(handle, &s1, planPref, workspacePref, &w1);
-        if (st == CUTENSOR_STATUS_SUCCESS) st = cutensorEstimateWorkspaceSize(handle, &s2, planPref, workspacePref, &w2);
+        cutensorStatus_t st = estimate(s1, w1);
+        if (st == CUTENSOR_STATUS_SUCCESS) st = estimate(s2, w2);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
-        *workspaceSizeEstimate = ((desc->tBytes + 255) & ~255ull) + std::max(w1, w2);
+        *workspaceSizeEstimate = align256(desc->tBytes) + std::max(w1, w2);
         return CUTENSOR_STATUS_SUCCESS;
     }
-    if (desc->kind == OpKind::Contraction) {
-        LoneSplit ls;     // the temporaries + the largest need of the reductions and the inner contraction — at WORKSPACE_MIN too: the
-        if (split_lone_modes(*desc, ls)) {     // temporaries are mandatory (the reference binding re-plans at MIN: einsum.cc:110)
-            uint64_t wI = 0, wA = 0, wB = 0;
-            cutensorStatus_t st = cutensorEstimateWorkspaceSize(handle, &ls.inner, planPref, workspacePref, &wI);
-            if (st == CUTENSOR_STATUS_SUCCESS && ls.hasA) st = cutensorEstimateWorkspaceSize(handle, &ls.redA, planPref, workspacePref, &wA);
-            if (st == CUTENSOR_STATUS_SUCCESS && ls.hasB) st = cutensorEstimateWorkspaceSize(handle, &ls.redB, planPref, workspacePref, &wB);
-            if (st != CUTENSOR_STATUS_SUCCESS) return st;
-            *workspaceSizeEstimate = ((ls.bytesA + 255) & ~255ull) + ((ls.bytesB + 255) & ~255ull) + std::max(wI, std::max(wA, wB));
-            return CUTENSOR_STATUS_SUCCESS;
-        }
+    TwoStepSplit ls;     // the temporaries + the largest need of the reductions and the inner contraction — at WORKSPACE_MIN too: the
+    if (desc->kind == OpKind::Contraction && split_lone_modes(*desc, ls)) {     // temporaries are mandatory (the reference binding re-plans at MIN: einsum.cc:110)
+        uint64_t wI = 0, wA = 0, wB = 0;
+        cutensorStatus_t st = estimate(ls.inner, wI);
+        if (st == CUTENSOR_STATUS_SUCCESS && ls.hasA) st = estimate(ls.stepA, wA);
+        if (st == CUTENSOR_STATUS_SUCCESS && ls.hasB) st = estimate(ls.stepB, wB);
+        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        *workspaceSizeEstimate = TwoStepLayout(ls.bytesA, ls.bytesB).offW + std::max(wI, std::max(wA, wB));
+        return CUTENSOR_STATUS_SUCCESS;
     }
     if (workspacePref == CUTENSOR_WORKSPACE_MIN) return CUTENSOR_STATUS_SUCCESS;
     const uint64_t cap = (workspacePref == CUTENSOR_WORKSPACE_MAX) ? (4ull << 30) : (1ull << 30);
-    if (desc->kind == OpKind::Contraction) {
-        ContractionView v;
-        cutensorStatus_t st = build_contraction_view(*desc, v, nullptr);
-        if (st != CUTENSOR_STATUS_SUCCESS) return st;
-        if (!v.wide && (v.dtype == HIP_R_16BF || v.dtype == HIP_R_16F)) {   // split-K partials of the 16-bit MFMA kernel
-            ContractionChoice hc;
-            RepackSplit rs;
-            const bool direct = pick_h16_choice(v, cap, handle->numCUs, hc);
-            const bool h16ok = desc->scalarType == HIP_R_32F && !(desc->compute && desc->compute->id == 5);
-            if (direct && !(h16ok && h16_sweep_waste(v))) *workspaceSizeEstimate = hc.workspace;
-            else if (h16ok && plan_repack(handle, *desc, v, cap, direct ? hc.estimateUs : -1.0, rs)) {
-                // operands copied into packed temporaries first (plan_repack): the temporaries + what the copies and the inner contraction want
-                const uint64_t temps = ((rs.bytesA + 255) & ~255ull) + ((rs.bytesB + 255) & ~255ull);
-                uint64_t wI = 0;
-                RepackScope scope;
-                cutensorStatus_t st2 = cutensorEstimateWorkspaceSize(handle, &rs.inner, planPref, workspacePref, &wI);
-                if (st2 != CUTENSOR_STATUS_SUCCESS) return st2;
-                *workspaceSizeEstimate = temps + wI;
-            } else if (direct || pick_gen_choice(v, cap, handle->numCUs, hc)) *workspaceSizeEstimate = hc.workspace;
-            return CUTENSOR_STATUS_SUCCESS;
-        }
-        if (!v.wide && (v.dtype == HIP_R_64F || v.dtype == HIP_C_32F || v.dtype == HIP_C_64F)) {   // split-K partials of the general MFMA family
-            ContractionChoice gc;
-            if (pick_gen_choice(v, cap, handle->numCUs, gc)) {
-                *workspaceSizeEstimate = gc.workspace;
-                RepackSplit rs;     // fp64 on element gathers: an operand copied first when that pays (plan_repack)
-                const double tDirect = desc->scalarType == v.dtype ? f64_direct_estimate_us(v, gc) : 0.0;
-                if (tDirect > 0.0 && plan_repack(handle, *desc, v, cap, tDirect, rs)) {
-                    const uint64_t temps = ((rs.bytesA + 255) & ~255ull) + ((rs.bytesB + 255) & ~255ull);
-                    uint64_t wI = 0;
-                    RepackScope scope;
-                    cutensorStatus_t st2 = cutensorEstimateWorkspaceSize(handle, &rs.inner, planPref, workspacePref, &wI);
-                    if (st2 != CUTENSOR_STATUS_SUCCESS) return st2;
-                    *workspaceSizeEstimate = temps + wI;
-                }
-            }
-            return CUTENSOR_STATUS_SUCCESS;
-        }
-        if (v.wide) {    // a peeled contraction wants what its inner, tiled problem wants
-            cutensorOperationDescriptor inner;
-            std::vector<PeelMode> peel;
-            if (peel_wide_contraction(*desc, inner, peel)) {
-                peel_fix_alignment(inner, peel);
-                return cutensorEstimateWorkspaceSize(handle, &inner, planPref, workspacePref, workspaceSizeEstimate);
-            }
-            return CUTENSOR_STATUS_SUCCESS;
-        }
-        if (v.dtype != HIP_R_32F) return CUTENSOR_STATUS_SUCCESS;
-        // the largest workspace any of the best few candidates would like to have
-        std::vector<ContractionChoice> ch = rank_contraction_choices(v, cap, handle->numCUs, planPref != nullptr && planPref->operandsStreamed != 0);
-        {   // reduced-precision compute descriptor: the same decision as cutensorCreatePlan — the split-K partials of that kernel
-            ContractionChoice gx;
-            std::string note;
-            const bool explicitPickX = planPref != nullptr && ((int)planPref->algo >= 0 || planPref->kernelRank > 0 || planPref->algo == CUTENSOR_ALGO_DEFAULT_PATIENT ||
-                                                               planPref->autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL);
-            if (f32x_decide(v, f32x_elem_of(*desc), cap, handle->numCUs, explicitPickX, ch, gx, note)) {
-                *workspaceSizeEstimate = gx.workspace;
-                return CUTENSOR_STATUS_SUCCESS;
-            }
-        }
-        {
-            RepackSplit rs;     // fp32 off the ring kernels: operands copied into packed temporaries first when that pays (plan_repack)
-            const double tDirect = f32_direct_estimate_us(v, ch);
-            if (tDirect > 0.0 && !(desc->compute && desc->compute->id == 5) && desc->scalarType == HIP_R_32F && plan_repack(handle, *desc, v, cap, tDirect, rs)) {
-                const uint64_t temps = ((rs.bytesA + 255) & ~255ull) + ((rs.bytesB + 255) & ~255ull);
-                uint64_t wI = 0;
-                RepackScope scope;
-                cutensorStatus_t st2 = cutensorEstimateWorkspaceSize(handle, &rs.inner, planPref, workspacePref, &wI);
-                if (st2 != CUTENSOR_STATUS_SUCCESS) return st2;
-                *workspaceSizeEstimate = temps + wI;
-                return CUTENSOR_STATUS_SUCCESS;
-            }
-        }
-        uint64_t want = 0;
-        for (size_t i = 0; i < ch.size() && i < 4; ++i) want = std::max(want, ch[i].workspace);
-        *workspaceSizeEstimate = want;
-    } else if (desc->kind == OpKind::Reduction) {
+    if (desc->kind == OpKind::Contraction) return estimate_contraction(handle, *desc, planPref, workspacePref, cap, workspaceSizeEstimate);
+    if (desc->kind == OpKind::Reduction) {
         ReducePlan rp;
-        cutensorStatus_t st = plan_reduction(*desc, cap, handle->numCUs, rp, nullptr);
+        const cutensorStatus_t st = plan_reduction(*desc, cap, handle->numCUs, rp, nullptr);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
         *workspaceSizeEstimate = rp.workspace;
     }
     return CUTENSOR_STATUS_SUCCESS;
 } CTAMD_API_CATCH
+
+// the fold that matches a kernel's split-K partials: accumulator-register order (fp32 ring kernels), row-major fp32, or — general family
+// with 8- / 16-byte elements — row-major partials in the accumulator type
+static hipError_t launch_splitk_fold(int family, const GettKernelInfo& k, const SplitKReduceParams& r, hipStream_t stream) {
+    if (family == 2 && !gen_elem_f32_partials(k.elem)) return launch_gen_splitk_reduce(r, k.elem, stream);
+    return k.fragPartials ? launch_splitk_reduce_frag(r, stream) : launch_splitk_reduce(r, stream);
+}
+
+// scratch tensors and an event pair of a measurement, released on every way out — an exception included (since round 5 the ABI turns
+// bad_alloc into a status code: what it unwinds through must not leak device memory in a process that keeps running)
+struct DeviceScratch {
+    void *A = nullptr, *B = nullptr, *D = nullptr, *W = nullptr, *T = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~DeviceScratch() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        for (void* p : {A, B, D, W, T}) if (p) (void)hipFree(p);
+    }
+    // A, B, D of the operation's own spans and a workspace; A and B hold finite, non-trivial data: 0x3c3c3c3c = 0.0115f (0x3c3c: 0.0115 in
+    // bf16, 1.06 in fp16)
+    bool alloc(const cutensorOperationDescriptor& op, size_t wsBytes) {
+        const size_t es = dtype_size(op.A.desc.dtype);
+        auto span = [&](const cutensorTensorDescriptor& d) { return (size_t)d.numElementsSpanned() * es; };
+        if (hipMalloc(&A, span(op.A.desc)) != hipSuccess || hipMalloc(&B, span(op.B.desc)) != hipSuccess || hipMalloc(&D, span(op.D.desc)) != hipSuccess ||
+            (wsBytes && hipMalloc(&W, wsBytes) != hipSuccess)) return false;
+        (void)hipMemset(A, 0x3c, span(op.A.desc));
+        (void)hipMemset(B, 0x3c, span(op.B.desc));
+        return true;
+    }
+    // the arguments of a launch on them: D = A B
+    void point(GettParams& gp, bool swapped) const {
+        gp.A = swapped ? B : A; gp.B = swapped ? A : B;
+        gp.endA += (unsigned long long)(uintptr_t)gp.A; gp.endB += (unsigned long long)(uintptr_t)gp.B;
+        gp.C = D; gp.D = D; gp.alpha = 1.f; gp.beta = 0.f;
+    }
+};
 
 // ---- measured selection for CUTENSOR_ALGO_DEFAULT_PATIENT -------------------------------------
 // Times the best-ranked candidates on scratch tensors of the problem's own shape; plan creation is
@@ -1207,64 +1233,32 @@ static int autotune_contraction(cutensorHandle_t handle, const cutensorOperation
     const int family = ch[0].family;             // 0 fp32 GETT, 1 aligned 16-bit (LDS-DMA), 2 general MFMA family — one table each
     for (const ContractionChoice& c : ch)
         if (c.family != family) return 0;        // mixed lists are not timed: a kernel index means nothing outside its own table
-    const size_t es = dtype_size(op.A.desc.dtype);
-    auto span = [&](const cutensorTensorDescriptor& d) {
-        int64_t n = 1;
-        for (uint32_t i = 0; i < d.numModes; ++i) n += (d.extent[i] - 1) * d.stride[i];
-        return (size_t)n * es;
-    };
     uint64_t wsMax = 0;
     const size_t nTry = std::min<size_t>(ch.size(), 12);
     for (size_t i = 0; i < nTry; ++i) wsMax = std::max(wsMax, ch[i].workspace);
-    // scratch tensors and the event pair, released on every way out — an exception included (since round 5 the ABI turns bad_alloc into a
-    // status code: what it unwinds through must not leak device memory in a process that keeps running)
-    struct Scratch {
-        void *A = nullptr, *B = nullptr, *D = nullptr, *W = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Scratch() {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            for (void* p : {A, B, D, W}) if (p) (void)hipFree(p);
-        }
-    } sc;
-    void *&A = sc.A, *&B = sc.B, *&D = sc.D, *&W = sc.W;
+    DeviceScratch sc;
+    void *&D = sc.D, *&W = sc.W;
     hipEvent_t &e0 = sc.e0, &e1 = sc.e1;
     int best = 0;
-    if (hipMalloc(&A, span(op.A.desc)) != hipSuccess || hipMalloc(&B, span(op.B.desc)) != hipSuccess ||
-        hipMalloc(&D, span(op.D.desc)) != hipSuccess || (wsMax && hipMalloc(&W, wsMax) != hipSuccess) ||
-        hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (!sc.alloc(op, wsMax) || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
         (void)hipGetLastError();
         return best;
     }
-    (void)hipMemset(A, 0x3c, span(op.A.desc));   // 0x3c3c3c3c = 0.0115f (0x3c3c: 0.0115 in bf16, 1.06 in fp16): finite, non-trivial data
-    (void)hipMemset(B, 0x3c, span(op.B.desc));
     {
         int count = 0;
-        const GettKernelInfo* tab = family == 2 ? gett_gen_kernels(&count) : family == 1 ? gett_h16_kernels(&count) : gett_f32_kernels(&count);
+        const GettKernelInfo* tab = kernel_table(family, &count);
         float bestMs = 1e30f;
         for (size_t i = 0; i < nTry; ++i) {
             GettParams gp;
             SplitKReduceParams rp;
             fill_gett_params(v, ch[i], gp, rp);
-            gp.A = v.swapped ? B : A;
-            gp.B = v.swapped ? A : B;
-            gp.endA += (unsigned long long)(uintptr_t)gp.A;
-            gp.endB += (unsigned long long)(uintptr_t)gp.B;
-            gp.C = D; gp.D = D; gp.alpha = 1.f; gp.beta = 0.f;
+            sc.point(gp, v.swapped);
             gp.partial = ch[i].splitK > 1 ? static_cast<float*>(W) : nullptr;
             rp.partial = static_cast<float*>(W); rp.C = D; rp.D = D; rp.alpha = 1.f; rp.beta = 0.f;
             // one launch = GETT kernel + (for split-K) the fold that matches the kernel's partial layout
             auto once = [&]() -> bool {
                 if (tab[ch[i].kernel].launch(gp, nullptr) != hipSuccess) return false;
-                if (ch[i].splitK > 1) {
-                    // the fold that matches the kernel's partials: accumulator-register order (fp32 stream kernels), row-major fp32, or —
-                    // general family with 8- / 16-byte elements — row-major partials in the accumulator type
-                    const int elem = family == 2 ? tab[ch[i].kernel].elem : GEN_BF16;
-                    const hipError_t e = (family == 2 && !gen_elem_f32_partials(elem)) ? launch_gen_splitk_reduce(rp, elem, nullptr)
-                                       : tab[ch[i].kernel].fragPartials ? launch_splitk_reduce_frag(rp, nullptr) : launch_splitk_reduce(rp, nullptr);
-                    if (e != hipSuccess) return false;
-                }
-                return true;
+                return ch[i].splitK <= 1 || launch_splitk_fold(family, tab[ch[i].kernel], rp, nullptr) == hipSuccess;
             };
             if (ch[i].kernel < 0 || ch[i].kernel >= count) continue;
             float ms = 1e30f;
@@ -1320,34 +1314,20 @@ static unsigned long long calibrate_xcd_split(cutensorHandle_t handle, const cut
         std::lock_guard<std::mutex> g(handle->mtx);
         if (handle->xcdSpeed.empty()) {
             handle->xcdSpeed.assign(8, 1.0);
-            const size_t es = 4;
-            auto span = [&](const cutensorTensorDescriptor& d) {
-                int64_t n = 1;
-                for (uint32_t i = 0; i < d.numModes; ++i) n += (d.extent[i] - 1) * d.stride[i];
-                return (size_t)n * es;
-            };
-            void *A = nullptr, *B = nullptr, *D = nullptr, *W = nullptr;
-            unsigned long long* T = nullptr;
+            DeviceScratch sc;
+            void *&W = sc.W, *&T = sc.T;
             const size_t tBytes = (size_t)splitK * 16 * sizeof(unsigned long long);
             std::vector<unsigned long long> host((size_t)splitK * 16);
-            bool ok = hipMalloc(&A, span(op.A.desc)) == hipSuccess && hipMalloc(&B, span(op.B.desc)) == hipSuccess &&
-                      hipMalloc(&D, span(op.D.desc)) == hipSuccess && hipMalloc(&W, pl.requiredWorkspace) == hipSuccess &&
-                      hipMalloc((void**)&T, tBytes) == hipSuccess;
+            bool ok = sc.alloc(op, pl.requiredWorkspace) && hipMalloc(&T, tBytes) == hipSuccess;
             if (ok) {
-                (void)hipMemset(A, 0x3c, span(op.A.desc));
-                (void)hipMemset(B, 0x3c, span(op.B.desc));
                 (void)hipMemset(T, 0, tBytes);
                 GettParams gp = pl.gett;
-                gp.A = pl.view.swapped ? B : A;
-                gp.B = pl.view.swapped ? A : B;
-                gp.endA += (unsigned long long)(uintptr_t)gp.A;
-                gp.endB += (unsigned long long)(uintptr_t)gp.B;
-                gp.C = D; gp.D = D; gp.alpha = 1.f; gp.beta = 0.f;
+                sc.point(gp, pl.view.swapped);
                 gp.partial = static_cast<float*>(W);
                 gp.sync = nullptr;
                 gp.xcdTiles = 0;
                 for (int rep = 0; rep < 4 && ok; ++rep) {
-                    gp.timing = (rep == 3) ? T : nullptr;
+                    gp.timing = (rep == 3) ? static_cast<unsigned long long*>(T) : nullptr;
                     ok = k.launch(gp, nullptr) == hipSuccess;
                 }
                 ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(host.data(), T, tBytes, hipMemcpyDeviceToHost) == hipSuccess;
@@ -1373,11 +1353,6 @@ static unsigned long long calibrate_xcd_split(cutensorHandle_t handle, const cut
             } else {
                 (void)hipGetLastError();
             }
-            if (A) (void)hipFree(A);
-            if (B) (void)hipFree(B);
-            if (D) (void)hipFree(D);
-            if (W) (void)hipFree(W);
-            if (T) (void)hipFree(T);
         }
     }
     // largest-remainder apportionment of perXcdSum tiles
@@ -1405,6 +1380,419 @@ static unsigned long long calibrate_xcd_split(cutensorHandle_t handle, const cut
         packed |= (unsigned long long)n[x] << (8 * x);
     }
     return uniform ? 0 : packed;
+}
+
+// ---- plan builders ------------------------------------------------------------------------------------------------
+// What cutensorCreatePlan was asked for.  A builder that returns `Built` answers nothing when the problem is not of its kind (the next
+// builder looks at it), else how building the plan went.  Sub-plans are created through cutensorCreatePlan itself (they go through the
+// plan memo like any other plan) and are owned by `pl` or by a local from the start.
+using Built = std::optional<cutensorStatus_t>;
+struct PlanRequest {
+    cutensorHandle*                    handle;
+    const cutensorOperationDescriptor& desc;
+    cutensorPlanPreference_t           pref;      // as the caller passed it (may be null): what sub-plans are created with
+    const cutensorPlanPreference&      pr;        // the same with the defaults filled in
+    uint64_t                           wsLimit;
+};
+static cutensorStatus_t create_sub_plan(const PlanRequest& rq, cutensorOperationDescriptor& d, uint64_t wsLimit, SubPlan& out) {
+    cutensorPlan_t p = nullptr;
+    const cutensorStatus_t st = cutensorCreatePlan(rq.handle, &p, &d, rq.pref, wsLimit);
+    out.reset(p);
+    return st;
+}
+// a plan the host loops of a peeled contraction can launch: one launch of a tiled (or the simple) kernel
+static bool plan_is_one_launch(const SubPlan& p) { return p->planKind != PlanKind::ModeTable && !p->sub1; }
+
+// E = alpha A B C + beta D: two pairwise plans and the intermediate at the head of the workspace
+static cutensorStatus_t build_trinary(const PlanRequest& rq, cutensorPlan& pl) {
+    const cutensorOperationDescriptor& desc = rq.desc;
+    const uint64_t tOff = align256(desc.tBytes);
+    if (rq.wsLimit < tOff) { CT_LOG("cutensorCreatePlan: trinary contraction needs %llu bytes for its intermediate", (unsigned long long)tOff); return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE; }
+    cutensorOperationDescriptor s1 = desc.sub[0], s2 = desc.sub[1];
+    cutensorStatus_t st = create_sub_plan(rq, s1, rq.wsLimit - tOff, pl.sub1);
+    if (st == CUTENSOR_STATUS_SUCCESS) st = create_sub_plan(rq, s2, rq.wsLimit - tOff, pl.sub2);
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    pl.tBytes = desc.tBytes;
+    for (int i = 0; i < 3; ++i) pl.triOrder[i] = desc.triOrder[i];
+    pl.alignB3 = desc.B.desc.alignment;            // B
+    pl.alignC = desc.C.desc.alignment;             // C (third input)
+    pl.alignD = desc.E.desc.alignment;             // output E (and its beta source D)
+    pl.requiredWorkspace = tOff + std::max(pl.sub1->requiredWorkspace, pl.sub2->requiredWorkspace);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+// a mode that one input alone carries (split_lone_modes): reduce the operand(s) over it into packed temporaries at the head of the
+// workspace, then contract
+static Built build_lone_reduce(const PlanRequest& rq, cutensorPlan& pl) {
+    TwoStepSplit ls;
+    if (!split_lone_modes(rq.desc, ls)) return {};
+    const TwoStepLayout lay(ls.bytesA, ls.bytesB);
+    if (rq.wsLimit < lay.offW) {
+        CT_LOG("cutensorCreatePlan: a contraction with a mode that one input alone carries needs %llu bytes for its temporaries", (unsigned long long)lay.offW);
+        return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;
+    }
+    cutensorStatus_t st = create_sub_plan(rq, ls.inner, rq.wsLimit - lay.offW, pl.sub1);
+    if (st == CUTENSOR_STATUS_SUCCESS && ls.hasA) st = create_sub_plan(rq, ls.stepA, rq.wsLimit - lay.offW, pl.loneA);
+    if (st == CUTENSOR_STATUS_SUCCESS && ls.hasB) st = create_sub_plan(rq, ls.stepB, rq.wsLimit - lay.offW, pl.loneB);
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    pl.loneBytesA = ls.bytesA; pl.loneBytesB = ls.bytesB;
+    if (rq.desc.A.desc.dtype == HIP_R_16F && rq.desc.scalarType == HIP_R_32F) {   // (loneShiftA: internal.hpp)
+        auto ceil_log2 = [](int64_t n) { int s = 0; while ((int64_t{1} << s) < n) ++s; return s; };
+        pl.loneShiftA = ls.hasA ? (ceil_log2(ls.summedA) + 1) / 2 : 0;
+        pl.loneShiftB = ls.hasB ? (ceil_log2(ls.summedB) + 1) / 2 : 0;
+    }
+    pl.planKind = PlanKind::LoneReduce;
+    pl.requiredWorkspace = lay.offW + std::max<uint64_t>(pl.sub1->requiredWorkspace, std::max<uint64_t>(pl.loneA ? pl.loneA->requiredWorkspace : 0, pl.loneB ? pl.loneB->requiredWorkspace : 0));
+    CT_LOG("plan: contraction with modes that one input alone carries -> %s%sreduced first (%llu + %llu bytes of temporaries), then the contraction",
+           pl.loneA ? "A " : "", pl.loneB ? "B " : "", (unsigned long long)ls.bytesA, (unsigned long long)ls.bytesB);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+// too many unfusable modes in a group for the tiled kernels (pl.view.wide): peel the smallest ones into a host loop if that takes at
+// most kMaxPeelLaunches launches (peel_wide_contraction); else the mode-table kernel takes the problem
+static Built build_peeled(const PlanRequest& rq, cutensorPlan& pl) {
+    if (!pl.view.wide || CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_PEEL", '0')) return {};
+    cutensorOperationDescriptor inner;
+    std::vector<PeelMode> peel;
+    if (!peel_wide_contraction(rq.desc, inner, peel)) return {};
+    peel_fix_alignment(inner, peel);
+    SubPlan ip, ip2;
+    if (create_sub_plan(rq, inner, rq.wsLimit, ip) != CUTENSOR_STATUS_SUCCESS || !plan_is_one_launch(ip)) return {};
+    // A peeled CONTRACTED mode accumulates into D: every launch after the first reads D as its C operand.  The inner plan carries the
+    // caller's C layout (and its conjugation); when that differs from D's, the accumulate launches get a second inner plan whose C
+    // descriptor is D's.
+    bool contracted = false;
+    int64_t launches = 1;
+    for (const PeelMode& pm : peel) { contracted = contracted || pm.contracted; launches *= pm.extent; }
+    if (contracted && (inner.C.desc.stride != inner.D.desc.stride || inner.C.op != CUTENSOR_OP_IDENTITY)) {
+        cutensorOperationDescriptor inner2 = inner;
+        inner2.C = inner.D;
+        inner2.C.op = CUTENSOR_OP_IDENTITY;
+        if (create_sub_plan(rq, inner2, rq.wsLimit, ip2) != CUTENSOR_STATUS_SUCCESS || !plan_is_one_launch(ip2)) return CUTENSOR_STATUS_NOT_SUPPORTED;
+        ip->requiredWorkspace = std::max(ip->requiredWorkspace, ip2->requiredWorkspace);
+    }
+    pl.requiredWorkspace = ip->requiredWorkspace;
+    pl.sub1 = std::move(ip);
+    pl.sub2 = std::move(ip2);
+    pl.peel = peel;
+    pl.planKind = PlanKind::Peeled;
+    CT_LOG("plan: contraction with an oversized mode group -> %zu mode(s) peeled, %lld launches of the tiled inner plan", peel.size(), (long long)launches);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+// conjugation flags follow the operands into their kernel roles (kernel-A is the user's B when swapped)
+static void set_conjugation(const cutensorOperationDescriptor& desc, bool swapped, int32_t& conjA, int32_t& conjB, int32_t& conjC) {
+    const bool cA = desc.A.op == CUTENSOR_OP_CONJ, cB = desc.B.op == CUTENSOR_OP_CONJ;
+    conjA = swapped ? cB : cA;
+    conjB = swapped ? cA : cB;
+    conjC = desc.C.op == CUTENSOR_OP_CONJ;
+}
+// the mode table of a plan in device memory (null: no memory, or no device)
+static std::shared_ptr<const WideMode> upload_mode_table(const std::vector<WideMode>& tab) {
+    void* dev = nullptr;
+    const size_t bytes = tab.size() * sizeof(WideMode);
+    std::shared_ptr<const WideMode> owner;
+    if (hipMalloc(&dev, bytes) == hipSuccess) owner.reset(static_cast<const WideMode*>(dev), [](const WideMode* p) { (void)hipFree(const_cast<WideMode*>(p)); });
+    if (owner && hipMemcpy(dev, tab.data(), bytes, hipMemcpyHostToDevice) == hipSuccess) return owner;
+    (void)hipGetLastError();
+    return nullptr;
+}
+// mode-table kernel (pl.view.wide): output modes (L, M, N), then contracted modes, in device memory owned by the plan
+static Built build_mode_table(const PlanRequest& rq, cutensorPlan& pl) {
+    if (!pl.view.wide) return {};
+    const ContractionView& v = pl.view;
+    std::vector<WideMode>& tab = pl.wideTab;
+    uint64_t outTotal = 1;
+    for (const std::vector<CanonMode>* g : {&v.L, &v.M, &v.N})
+        for (const CanonMode& m : *g) {
+            tab.push_back(WideMode{make_fastdiv((uint32_t)m.extent), m.sA, m.sB, m.sC, m.sD});
+            outTotal *= (uint64_t)m.extent;
+        }
+    pl.wide.nOut = (uint32_t)tab.size();
+    for (const CanonMode& m : v.K) tab.push_back(WideMode{make_fastdiv((uint32_t)m.extent), m.sA, m.sB, 0, 0});
+    pl.wide.nK = (uint32_t)v.K.size();
+    pl.wide.outTotal = outTotal;
+    pl.wide.kTotal = (uint32_t)v.totK;
+    set_conjugation(rq.desc, v.swapped, pl.wide.conjA, pl.wide.conjB, pl.wide.conjC);
+    if (tab.empty()) tab.push_back(WideMode{make_fastdiv(1), 0, 0, 0, 0});
+    // The table goes to device memory HERE when the handle has a device — on the handle's device, outside any stream capture, so that
+    // cutensorContract neither allocates nor synchronises (it may be called while a graph is being captured).  Handles without a
+    // device (plan-only, the CPU tests) keep the host copy: planning needs no GPU, and a plan that one of those hands to a process
+    // with a GPU uploads at first execution (launch_mode_table).
+    if (rq.handle->haveDevice) {
+        int prev = -1;
+        const bool switched = hipGetDevice(&prev) == hipSuccess && prev != rq.handle->device && hipSetDevice(rq.handle->device) == hipSuccess;
+        pl.wideDev = upload_mode_table(tab);
+        if (switched) (void)hipSetDevice(prev);
+    }
+    pl.planKind = PlanKind::ModeTable;
+    pl.requiredWorkspace = 0;
+    CT_LOG("plan: contraction with %u output + %u contracted unfusable modes -> mode-table kernel", pl.wide.nOut, pl.wide.nK);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+// The ranked candidates of a contraction the tiled kernels can describe, and what its repack builder needs to know about them
+struct TiledRoute {
+    bool mfmaPath = false, h16Path = false, genPath = false;   // fp32 families / aligned 16-bit family / general MFMA family (h16Path implies genPath)
+    std::vector<ContractionChoice> ch;                         // best first; empty: the general family or the simple kernel
+    double tDirectUs = 0.0;                                    // > 0: fp32 / fp64 / complex64 off their fast kernels — what the plan on the operands as they lie costs
+    int family() const { return mfmaPath ? 0 : h16Path ? 1 : 2; }
+};
+static TiledRoute rank_tiled_candidates(const PlanRequest& rq, const cutensorPlan& pl) {
+    const cutensorOperationDescriptor& desc = rq.desc;
+    const ContractionView& v = pl.view;
+    const int numCUs = rq.handle->numCUs;
+    TiledRoute r;
+    r.mfmaPath = v.dtype == HIP_R_32F && !pl.accumulate64;
+    r.h16Path = !r.mfmaPath && !pl.accumulate64 && desc.scalarType == HIP_R_32F && (v.dtype == HIP_R_16BF || v.dtype == HIP_R_16F);
+    // general MFMA family: 16-bit shapes the aligned kernels refuse, fp64 (double scalars), complex (complex scalars)
+    r.genPath = r.h16Path || (v.dtype == HIP_R_64F && desc.scalarType == HIP_R_64F) ||
+                (v.dtype == HIP_C_32F && desc.scalarType == HIP_C_32F && !pl.accumulate64) ||
+                (v.dtype == HIP_C_64F && desc.scalarType == HIP_C_64F);
+    if (r.mfmaPath) r.ch = rank_contraction_choices(v, rq.wsLimit, numCUs, rq.pr.operandsStreamed != 0);
+    else if (r.h16Path && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", 'f'))   // "force" (measurement): the general family also where the aligned 16-bit kernels apply
+        r.ch = rank_h16_choices(v, rq.wsLimit, numCUs);
+    if (r.mfmaPath && desc.scalarType == HIP_R_32F && !names_candidate(rq.pr) && !ctamd_research_env("CUTENSOR_AMD_KORDER"))
+        r.tDirectUs = f32_direct_estimate_us(v, r.ch);
+    if (r.mfmaPath) {
+        // a reduced-precision compute descriptor: the bf16 / fp16-rate kernels when the model (or CUTENSOR_AMD_F32X=force) says so.
+        // They take the operands as they lie (no repack pre-pass); a caller who names a candidate addresses the fp32 list as ever.
+        const int xe = f32x_elem_of(desc);
+        ContractionChoice gx;
+        std::string note;
+        if (xe >= 0 && f32x_decide(v, xe, rq.wsLimit, numCUs, names_candidate_or_tunes(rq.pr), r.ch, gx, note)) {
+            r.ch.assign(1, gx);
+            r.tDirectUs = 0.0;
+        }
+        if (xe >= 0 && !note.empty()) CT_LOG("plan: fp32 contraction, compute descriptor %s: %s", xe == GEN_F32_F16 ? "16F" : xe == GEN_F32_BF16 ? "16BF" : "TF32", note.c_str());
+    }
+    if ((v.dtype == HIP_R_64F || v.dtype == HIP_C_32F) && desc.scalarType == v.dtype && r.genPath && r.ch.empty()) {   // fp64 / complex64 on element gathers (plan_repack)
+        ContractionChoice g64;
+        if (pick_gen_choice(v, rq.wsLimit, numCUs, g64)) r.tDirectUs = f64_direct_estimate_us(v, g64);
+    }
+    return r;
+}
+// The LDS-DMA kernels refuse the operands as they lie (or would spend most of every K-tile on the padding of a short ragged contracted
+// mode), or fp32 / fp64 / complex64 data is off its fast kernels: copy operands into packed temporaries first when that pays (plan_repack)
+static Built build_repack(const PlanRequest& rq, cutensorPlan& pl, const TiledRoute& r) {
+    const bool h16Refused = r.h16Path && (r.ch.empty() || h16_sweep_waste(pl.view)) && !CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") && !CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES");
+    if (!(h16Refused || r.tDirectUs > 0.0) || names_candidate(rq.pr) ||      // (a caller who names a candidate gets that candidate)
+        CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_REPACK", '0'))
+        return {};
+    TwoStepSplit rs;
+    if (!plan_repack(rq.handle, rq.desc, pl.view, rq.wsLimit, r.tDirectUs > 0.0 ? r.tDirectUs : r.ch.empty() ? -1.0 : r.ch[0].estimateUs, rs)) return {};
+    const TwoStepLayout lay(rs.bytesA, rs.bytesB);
+    SubPlan pi, pa, pb;
+    cutensorStatus_t st;
+    {
+        RepackScope scope;
+        st = create_sub_plan(rq, rs.inner, rq.wsLimit - lay.offW, pi);
+    }
+    if (st == CUTENSOR_STATUS_SUCCESS && rs.hasA) st = create_sub_plan(rq, rs.stepA, 0, pa);
+    if (st == CUTENSOR_STATUS_SUCCESS && rs.hasB) st = create_sub_plan(rq, rs.stepB, 0, pb);
+    // (the copies or the inner plan refused: the general family takes the problem as it is)
+    if (st != CUTENSOR_STATUS_SUCCESS || pi->choice.family != r.family() || pi->sub1) return {};
+    pl.requiredWorkspace = lay.offW + pi->requiredWorkspace;
+    pl.sub1 = std::move(pi); pl.loneA = std::move(pa); pl.loneB = std::move(pb);
+    pl.loneBytesA = rs.bytesA; pl.loneBytesB = rs.bytesB;
+    pl.planKind = PlanKind::Repack;
+    CT_LOG("plan: 16-bit contraction whose operands the LDS-DMA kernels cannot stage -> %s%scopied into packed temporaries first (%llu + %llu bytes), then the contraction",
+           pl.loneA ? "A " : "", pl.loneB ? "B " : "", (unsigned long long)rs.bytesA, (unsigned long long)rs.bytesB);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+// Which of the ranked candidates `ch` (not empty) the plan takes: an incremental-autotuning trial, the plan cache's entry, the
+// candidate the caller names, the measured one (PATIENT) — else the first
+static size_t select_candidate(const PlanRequest& rq, cutensorPlan& pl, const std::vector<ContractionChoice>& ch) {
+    cutensorHandle* handle = rq.handle;
+    const cutensorPlanPreference& pr = rq.pr;
+    size_t idx = 0;
+    // (a plan made under the "operands are streamed" preference neither reads nor feeds the per-problem cache: the cache is keyed by
+    // the problem alone, and its entry belongs to the default policy)
+    const bool useCache = handle->planCacheCapacity > 0 && pr.cacheMode != CUTENSOR_CACHE_MODE_NONE && pr.operandsStreamed == 0;
+    const bool explicitPick = names_candidate(pr);   // the caller names a candidate: the cache has no say
+    const bool incremental = useCache && !explicitPick && pr.autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL;
+    const bool patient = pr.algo == CUTENSOR_ALGO_DEFAULT_PATIENT;
+    bool needKey = incremental || (useCache && patient);
+    if (useCache && !explicitPick && !needKey) {
+        std::lock_guard<std::mutex> g(handle->mtx);
+        needKey = !handle->planCache.empty();
+    }
+    const std::string key = needKey ? problem_key(rq.desc) : std::string();   // the string form is what the cache FILE holds
+    // incremental autotuning (contraction_plan_cache.cu:215-237): the first INCREMENTAL_COUNT plans of a problem
+    // are trials of candidates 0, 1, ... (timed by cutensorContract: the best of a trial plan's first few executions);
+    // after that — and for every plan without the autotune mode — the cache answers with the fastest candidate
+    // measured so far.  (The sample's loop is count + 1 rounds of which the last must hit the cache, :262.)
+    if (incremental) {
+        resolve_pending_measurements(handle);
+        std::lock_guard<std::mutex> g(handle->mtx);
+        auto tit = handle->tuning.find(key);
+        if (tit == handle->tuning.end() && handle->tuning.size() < std::max<size_t>(handle->planCacheCapacity, 1))
+            tit = handle->tuning.emplace(key, cutensorHandle::TuneState{}).first;   // bounded like the cache itself
+        if (tit != handle->tuning.end()) {
+            cutensorHandle::TuneState& t = tit->second;
+            const int limit = std::min<int>(std::max<int32_t>(pr.incrementalCount, 1), (int)ch.size());
+            if (t.next < limit) {
+                pl.tuneKey = key;
+                return (size_t)t.next++;
+            }
+        }
+    }
+    if (useCache && !explicitPick) {
+        std::lock_guard<std::mutex> g(handle->mtx);
+        auto it = needKey ? handle->planCache.find(key) : handle->planCache.end();
+        if (it != handle->planCache.end())
+            for (size_t i = 0; i < ch.size(); ++i)
+                if (ch[i].kernel == it->second.kernel && ch[i].splitK == it->second.splitK) return i;
+    }
+    if ((int)pr.algo >= 0) idx = std::min<size_t>((size_t)pr.algo, ch.size() - 1);
+    else if (pr.kernelRank > 0) idx = std::min<size_t>((size_t)pr.kernelRank, ch.size() - 1);
+    else if (patient) idx = (size_t)autotune_contraction(handle, rq.desc, pl.view, ch);
+    if (const char* f = ctamd_research_env("CUTENSOR_AMD_FORCE")) {   // "kernel:splitK" experiment knob
+        int fk = -1; unsigned fs = 1;
+        if (std::sscanf(f, "%d:%u", &fk, &fs) >= 1)
+            for (size_t i = 0; i < ch.size(); ++i)
+                if (ch[i].kernel == fk && ch[i].splitK == fs) { idx = i; break; }
+    }
+    if (useCache && patient) {
+        std::lock_guard<std::mutex> g(handle->mtx);
+        if (handle->planCache.size() < handle->planCacheCapacity) {
+            handle->planCache[key] = PlanCacheEntry{key, ch[idx].kernel, ch[idx].splitK};
+            handle->planMemo.clear();   // a DEFAULT prototype memoised earlier must not shadow the measured choice
+        }
+    }
+    return idx;
+}
+// the two opt-in refinements of a split-K plan on the fp32 ring kernels: a per-XCD K split and the in-launch fold
+static void tune_f32_splitk(const PlanRequest& rq, cutensorPlan& pl) {
+    const ContractionChoice& pick = pl.choice;
+    if (pl.planKind != PlanKind::Tiled || pick.family != 0 || pick.splitK <= 1) return;
+    const GettKernelInfo& k = *kernel_info(0, pick.kernel);
+    if (!k.fragPartials || k.ablation) return;
+    // Per-XCD K split (one output tile, split-K over whole XCD rows): see calibrate_xcd_split.  Opt-in: on the parts measured the clocks
+    // differ by +-1.5 %, below the 1-tile-in-32 (3 %) granularity of the headline split, so the apportionment comes out uniform
+    // 
+    if (pick.splitK >= 64 && pl.view.totL == 1 && pl.gett.tilesM * pl.gett.tilesN == 1) {
+        const char* env = ctamd_research_env("CUTENSOR_AMD_XCD_BALANCE");
+        if (env && env[0] == '1') pl.gett.xcdTiles = calibrate_xcd_split(rq.handle, rq.desc, pl);
+    }
+    // In-launch fold of the split-K partials: only when every workgroup of the launch owns a CU of its own (they wait for each other)
+    // and the output is a plain matrix; otherwise the fold is a second kernel.  Opt-in: measured slower than the two-kernel fold
+    if (CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_FUSED_FOLD", '1') && pl.gett.nBlocks <= (uint32_t)rq.handle->numCUs && pl.view.totL == 1 &&
+        pl.view.M.size() <= 1 && pl.view.N.size() <= 1) {
+        std::lock_guard<std::mutex> g(rq.handle->mtx);
+        if (rq.handle->syncPool == nullptr) {
+            void* ptr = nullptr;
+            const size_t bytes = (size_t)cutensorHandle::kSyncSlots * 64;
+            if (hipMalloc(&ptr, bytes) == hipSuccess && hipMemset(ptr, 0, bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess)
+                rq.handle->syncPool = static_cast<uint32_t*>(ptr);
+            else
+                (void)hipGetLastError();
+        }
+        pl.fusedFold = rq.handle->syncPool != nullptr;
+    }
+}
+static void log_tiled_plan(const cutensorPlan& pl) {
+    if (log_level() <= 0) return;
+    const ContractionView& v = pl.view;
+    const ContractionChoice& pick = pl.choice;
+    const unsigned long long L = v.totL, M = v.totM, N = v.totN, K = v.totK;
+    if (pl.planKind == PlanKind::Simple) { CT_LOG("plan: contraction -> simple kernel (dtype %d)", (int)v.dtype); return; }
+    const GettKernelInfo& k = *kernel_info(pick.family, pick.kernel);
+    if (pick.family == 2)
+        CT_LOG("plan: contraction (general MFMA family) dtype=%d L=%llu M=%llu N=%llu K=%llu swapped=%d -> gen kernel %d (%dx%dx%d orientA=%d orientB=%d V=%d) splitK=%u",
+               (int)v.dtype, L, M, N, K, (int)v.swapped, pick.kernel, k.bm, k.bn, k.bk, k.layA, k.layB, k.vec, pick.splitK);
+    else if (pick.family == 1)
+        CT_LOG("plan: contraction (16-bit MFMA) L=%llu M=%llu N=%llu K=%llu layA=%d layB=%d swapped=%d -> h16 kernel %d", L, M, N, K, v.layA, v.layB,
+               (int)v.swapped, pick.kernel);
+    else
+        CT_LOG("plan: contraction L=%llu M=%llu N=%llu K=%llu layA=%d layB=%d swapped=%d -> kernel %d (%dx%dx%d) splitK=%u ws=%llu est=%.1fus", L, M, N, K,
+               v.layA, v.layB, (int)v.swapped, pick.kernel, k.bm, k.bn, k.bk, pick.splitK, (unsigned long long)pick.workspace, pick.estimateUs);
+}
+// one launch of a tiled kernel (+ the split-K fold), or of the simple kernel when no family has a candidate
+static cutensorStatus_t build_tiled(const PlanRequest& rq, cutensorPlan& pl, TiledRoute& r) {
+    if (r.ch.empty() && r.genPath && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0')) {
+        ContractionChoice g;
+        if (pick_gen_choice(pl.view, rq.wsLimit, rq.handle->numCUs, g)) r.ch.push_back(g);
+    }
+    if (!r.ch.empty()) pl.choice = r.ch[select_candidate(rq, pl, r.ch)];
+    pl.planKind = pl.choice.kernel >= 0 ? PlanKind::Tiled : PlanKind::Simple;
+    fill_gett_params(pl.view, pl.choice, pl.gett, pl.skr);
+    set_conjugation(rq.desc, pl.view.swapped, pl.gett.conjA, pl.gett.conjB, pl.gett.conjC);
+    pl.requiredWorkspace = pl.choice.workspace;
+    if (r.mfmaPath) tune_f32_splitk(rq, pl);
+    log_tiled_plan(pl);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+static cutensorStatus_t build_contraction(const PlanRequest& rq, cutensorPlan& pl) {
+    if (const Built b = build_lone_reduce(rq, pl)) return *b;
+    const cutensorStatus_t st = build_contraction_view(rq.desc, pl.view, nullptr);
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    if (const Built b = build_peeled(rq, pl)) return *b;
+    // complex data only multiplies on the general MFMA family or on the mode-table kernel (complex scalars of the data's type)
+    const bool cplx = pl.view.dtype == HIP_C_32F || pl.view.dtype == HIP_C_64F;
+    if (cplx && (CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0') || rq.desc.scalarType != pl.view.dtype || (pl.view.dtype == HIP_C_32F && pl.accumulate64)))
+        pl.view.wide = true;
+    if (const Built b = build_mode_table(rq, pl)) return *b;
+    TiledRoute r = rank_tiled_candidates(rq, pl);
+    if (const Built b = build_repack(rq, pl, r)) return *b;
+    return build_tiled(rq, pl, r);
+}
+// The output buffer of a padded permutation is the packed tensor of extents e + padLeft + padRight (the sample sizes it that way,
+// elementwise_permute_padding.cu:101-103); the descriptor carries the unpadded extents.
+static cutensorStatus_t build_padded_permutation(const PlanRequest& rq, cutensorPlan& pl) {
+    const cutensorOperationDescriptor& desc = rq.desc;
+    const size_t nm = desc.D.modes.size();
+    std::vector<int64_t> padded(nm);
+    int64_t accU = 1, accP = 1, offset = 0;
+    bool isPacked = true;
+    for (size_t i = 0; i < nm; ++i) {
+        const int64_t l = desc.padLeft.empty() ? 0 : desc.padLeft[i], r = desc.padRight.empty() ? 0 : desc.padRight[i];
+        padded[i] = accP;
+        isPacked = isPacked && (desc.D.desc.extent[i] == 1 || desc.D.desc.stride[i] == accU);
+        offset += l * accP;
+        accU *= desc.D.desc.extent[i];
+        accP *= desc.D.desc.extent[i] + l + r;
+    }
+    if (!isPacked) { CT_LOG("cutensorCreatePlan: padding needs a packed output descriptor"); return CUTENSOR_STATUS_NOT_SUPPORTED; }
+    cutensorOperationDescriptor inner = desc;
+    inner.D.desc.stride = padded;
+    // the interior starts `offset` elements into the buffer: keep the 16-byte-lane variants only if that is lane-aligned
+    const int64_t lane = 16 / (int64_t)dtype_size(desc.D.desc.dtype);
+    if (offset % lane != 0) inner.D.desc.alignment = (uint32_t)dtype_size(desc.D.desc.dtype);
+    const cutensorStatus_t st = plan_elementwise(inner, pl.ew, nullptr);
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    pl.padFillElems = (uint64_t)accP;
+    pl.padOffsetElems = offset;
+    pl.padValue = desc.padValue;
+    CT_LOG("plan: padded permutation variant=%d fill=%llu elems offset=%lld", pl.ew.variant, (unsigned long long)pl.padFillElems, (long long)offset);
+    return CUTENSOR_STATUS_SUCCESS;
+}
+// element-wise operations and reductions: one planner call each
+static cutensorStatus_t build_elementwise(const PlanRequest& rq, cutensorPlan& pl) {
+    const cutensorOperationDescriptor& desc = rq.desc;
+    if (desc.kind == OpKind::Reduction) {
+        const cutensorStatus_t st = plan_reduction(desc, rq.wsLimit, rq.handle->numCUs, pl.red, nullptr);
+        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        pl.requiredWorkspace = pl.red.workspace;
+        CT_LOG("plan: reduction variant=%d kept=%u red=%u splitR=%u perm=%d", pl.red.variant, pl.red.p.kept.total, pl.red.p.red.total, pl.red.p.splitR,
+               (int)pl.red.isPermutation);
+    } else if (desc.kind == OpKind::ElementwiseTrinary) {
+        const cutensorStatus_t st = plan_elementwise_trinary(desc, pl.ew3, nullptr);
+        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        pl.alignB3 = desc.B.desc.alignment;
+        CT_LOG("plan: elementwise trinary passes=%d swapAB=%d bothPermuted=%d variant(last)=%d", pl.ew3.twoPass ? 2 : 1, (int)pl.ew3.swapAB,
+               (int)pl.ew3.bothPermuted, pl.ew3.last.variant);
+    } else {
+        const cutensorStatus_t st = plan_elementwise(desc, pl.ew, nullptr);
+        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        CT_LOG("plan: elementwise variant=%d E0=%u E1=%u rest=%u blocks=%u", pl.ew.variant, pl.ew.p.E0, pl.ew.p.E1, pl.ew.p.rest.total, pl.ew.p.nBlocks);
+    }
+    return CUTENSOR_STATUS_SUCCESS;
+}
+static cutensorStatus_t build_plan(const PlanRequest& rq, cutensorPlan& pl) {
+    switch (rq.desc.kind) {
+        case OpKind::BlockSparseContraction: return blocksparse_plan(rq.handle, rq.desc, rq.wsLimit, &pl);
+        case OpKind::ContractionTrinary:     return build_trinary(rq, pl);
+        case OpKind::Contraction:            return build_contraction(rq, pl);
+        default:   // reductions and the element-wise operations; CUTENSOR_OPERATION_DESCRIPTOR_PADDING_* is accepted on permutations only
+            return (rq.desc.padLeft.empty() && rq.desc.padRight.empty()) ? build_elementwise(rq, pl) : build_padded_permutation(rq, pl);
+    }
 }
 
 // contraction.cu:218-222, elementwise_permute.cu:183-187 (limit 0), einsum.cu:324-329 (limit 1 GiB)
@@ -1443,9 +1831,8 @@ cutensorStatus_t cutensorCreatePlan(const cutensorHandle_t handle, cutensorPlan_
         handle->memoMisses.fetch_add(1, std::memory_order_relaxed);
     }
     // the plan under construction is owned here until it is handed to the caller: an exception below (bad_alloc in a planner's vectors,
-    // caught by the barrier at the end) or an early return frees it together with its sub-plans (round-5 advice)
-    std::unique_ptr<cutensorPlan> owner(new (std::nothrow) cutensorPlan());
-    cutensorPlan* const pl = owner.get();
+    // caught by the barrier at the end) or a failed builder frees it together with its sub-plans
+    std::unique_ptr<cutensorPlan> pl(new (std::nothrow) cutensorPlan());
     if (pl == nullptr) return CUTENSOR_STATUS_ALLOC_FAILED;
     pl->kind = desc->kind;
     pl->dtype = desc->A.desc.dtype;
@@ -1455,413 +1842,13 @@ cutensorStatus_t cutensorCreatePlan(const cutensorHandle_t handle, cutensorPlan_
     pl->alignC = desc->C.present ? desc->C.desc.alignment : 0;
     pl->alignD = desc->D.desc.alignment;
     pl->accumulate64 = desc->compute && desc->compute->id == 5;
-    std::string why;
-    cutensorStatus_t st = CUTENSOR_STATUS_SUCCESS;
-
-    if (desc->kind == OpKind::BlockSparseContraction) {
-        st = blocksparse_plan(handle, *desc, workspaceSizeLimit, pl);
-        if (st != CUTENSOR_STATUS_SUCCESS) { return st; }
-        *plan = owner.release();
-        return CUTENSOR_STATUS_SUCCESS;
-    }
-    if (desc->kind == OpKind::ContractionTrinary) {
-        const uint64_t tOff = (desc->tBytes + 255) & ~255ull;
-        if (workspaceSizeLimit < tOff) { CT_LOG("cutensorCreatePlan: trinary contraction needs %llu bytes for its intermediate", (unsigned long long)tOff); return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE; }
-        cutensorOperationDescriptor s1 = desc->sub[0], s2 = desc->sub[1];
-        cutensorPlan_t p1 = nullptr, p2 = nullptr;
-        st = cutensorCreatePlan(handle, &p1, &s1, pref, workspaceSizeLimit - tOff);
-        if (st == CUTENSOR_STATUS_SUCCESS) st = cutensorCreatePlan(handle, &p2, &s2, pref, workspaceSizeLimit - tOff);
-        if (st != CUTENSOR_STATUS_SUCCESS) { delete p1; delete p2; return st; }
-        pl->sub1 = p1; pl->sub2 = p2;
-        pl->tBytes = desc->tBytes;
-        for (int i = 0; i < 3; ++i) pl->triOrder[i] = desc->triOrder[i];
-        pl->alignB3 = desc->B.desc.alignment;            // B
-        pl->alignC = desc->C.desc.alignment;             // C (third input)
-        pl->alignD = desc->E.desc.alignment;             // output E (and its beta source D)
-        pl->requiredWorkspace = tOff + std::max(p1->requiredWorkspace, p2->requiredWorkspace);
-        *plan = owner.release();
-        return CUTENSOR_STATUS_SUCCESS;
-    }
-
-    if (desc->kind == OpKind::Contraction) {
-        LoneSplit ls;
-        if (split_lone_modes(*desc, ls)) {
-            // reduce the operand(s) over the modes nothing else carries into packed temporaries at the head of the workspace, then contract
-            const uint64_t offB = (ls.bytesA + 255) & ~255ull, offW = offB + ((ls.bytesB + 255) & ~255ull);
-            if (workspaceSizeLimit < offW) { CT_LOG("cutensorCreatePlan: a contraction with a mode that one input alone carries needs %llu bytes for its temporaries", (unsigned long long)offW); return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE; }
-            cutensorPlan_t pi = nullptr, pa = nullptr, pb = nullptr;
-            st = cutensorCreatePlan(handle, &pi, &ls.inner, pref, workspaceSizeLimit - offW);
-            if (st == CUTENSOR_STATUS_SUCCESS && ls.hasA) st = cutensorCreatePlan(handle, &pa, &ls.redA, pref, workspaceSizeLimit - offW);
-            if (st == CUTENSOR_STATUS_SUCCESS && ls.hasB) st = cutensorCreatePlan(handle, &pb, &ls.redB, pref, workspaceSizeLimit - offW);
-            if (st != CUTENSOR_STATUS_SUCCESS) { delete pi; delete pa; delete pb; return st; }
-            pl->sub1 = pi; pl->loneA = pa; pl->loneB = pb;
-            pl->loneBytesA = ls.bytesA; pl->loneBytesB = ls.bytesB;
-            if (desc->A.desc.dtype == HIP_R_16F && desc->scalarType == HIP_R_32F) {   // (loneShiftA: internal.hpp)
-                auto ceil_log2 = [](int64_t n) { int s = 0; while ((int64_t{1} << s) < n) ++s; return s; };
-                pl->loneShiftA = ls.hasA ? (ceil_log2(ls.summedA) + 1) / 2 : 0;
-                pl->loneShiftB = ls.hasB ? (ceil_log2(ls.summedB) + 1) / 2 : 0;
-            }
-            pl->choice = ContractionChoice{};
-            pl->choice.kernel = -4;
-            pl->requiredWorkspace = offW + std::max<uint64_t>(pi->requiredWorkspace, std::max<uint64_t>(pa ? pa->requiredWorkspace : 0, pb ? pb->requiredWorkspace : 0));
-            CT_LOG("plan: contraction with modes that one input alone carries -> %s%sreduced first (%llu + %llu bytes of temporaries), then the contraction",
-                   pa ? "A " : "", pb ? "B " : "", (unsigned long long)ls.bytesA, (unsigned long long)ls.bytesB);
-            if (memoable) memo_insert(handle, mkey, mhash, *pl);
-            *plan = owner.release();
-            return CUTENSOR_STATUS_SUCCESS;
-        }
-        st = build_contraction_view(*desc, pl->view, &why);
-        if (st != CUTENSOR_STATUS_SUCCESS) { return st; }
-        if (pl->view.wide && !(CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") && CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL")[0] == '0')) {
-            // too many unfusable modes in a group for the tiled kernels: peel the smallest ones into a host loop if that takes
-            // at most kMaxPeelLaunches launches (peel_wide_contraction), else fall through to the mode-table kernel
-            cutensorOperationDescriptor inner;
-            std::vector<PeelMode> peel;
-            if (peel_wide_contraction(*desc, inner, peel)) {
-                peel_fix_alignment(inner, peel);
-                cutensorPlan_t ip = nullptr;
-                if (cutensorCreatePlan(handle, &ip, &inner, pref, workspaceSizeLimit) == CUTENSOR_STATUS_SUCCESS && ip->choice.kernel != -2 &&
-                    ip->sub1 == nullptr) {
-                    // A peeled CONTRACTED mode accumulates into D: every launch after the first reads D as its C operand.  The inner
-                    // plan carries the caller's C layout (and its conjugation); when that differs from D's, the accumulate launches
-                    // get a second inner plan whose C descriptor is D's.
-                    bool contracted = false;
-                    for (const PeelMode& pm : peel) contracted = contracted || pm.contracted;
-                    if (contracted && (inner.C.desc.stride != inner.D.desc.stride || inner.C.op != CUTENSOR_OP_IDENTITY)) {
-                        cutensorOperationDescriptor inner2 = inner;
-                        inner2.C = inner.D;
-                        inner2.C.op = CUTENSOR_OP_IDENTITY;
-                        cutensorPlan_t ip2 = nullptr;
-                        if (cutensorCreatePlan(handle, &ip2, &inner2, pref, workspaceSizeLimit) != CUTENSOR_STATUS_SUCCESS || ip2->choice.kernel == -2 ||
-                            ip2->sub1 != nullptr) {
-                            delete ip2;
-                            delete ip;
-                            
-                            return CUTENSOR_STATUS_NOT_SUPPORTED;
-                        }
-                        pl->sub2 = ip2;
-                        ip->requiredWorkspace = std::max(ip->requiredWorkspace, ip2->requiredWorkspace);
-                    }
-                    pl->sub1 = ip;
-                    pl->peel = peel;
-                    pl->choice = ContractionChoice{};
-                    pl->choice.kernel = -3;
-                    pl->requiredWorkspace = ip->requiredWorkspace;
-                    int64_t launches = 1;
-                    for (const PeelMode& pm : peel) launches *= pm.extent;
-                    CT_LOG("plan: contraction with an oversized mode group -> %zu mode(s) peeled, %lld launches of the tiled inner plan", peel.size(), (long long)launches);
-                    *plan = owner.release();
-                    return CUTENSOR_STATUS_SUCCESS;
-                }
-                delete ip;
-            }
-        }
-        {
-            const bool cplx = pl->view.dtype == HIP_C_32F || pl->view.dtype == HIP_C_64F;
-            const bool genOff = CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") && CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN")[0] == '0';
-            // complex data only multiplies on the general MFMA family or on the mode-table kernel (complex scalars of the data's type)
-            if (cplx && (genOff || desc->scalarType != pl->view.dtype || (pl->view.dtype == HIP_C_32F && pl->accumulate64))) pl->view.wide = true;
-        }
-        if (pl->view.wide) {
-            // mode-table kernel: output modes (L, M, N), then contracted modes, in device memory owned by the plan
-            const ContractionView& v = pl->view;
-            std::vector<WideMode> tab;
-            uint64_t outTotal = 1;
-            for (const std::vector<CanonMode>* g : {&v.L, &v.M, &v.N})
-                for (const CanonMode& m : *g) {
-                    tab.push_back(WideMode{make_fastdiv((uint32_t)m.extent), m.sA, m.sB, m.sC, m.sD});
-                    outTotal *= (uint64_t)m.extent;
-                }
-            pl->wide.nOut = (uint32_t)tab.size();
-            for (const CanonMode& m : v.K) tab.push_back(WideMode{make_fastdiv((uint32_t)m.extent), m.sA, m.sB, 0, 0});
-            pl->wide.nK = (uint32_t)v.K.size();
-            pl->wide.outTotal = outTotal;
-            pl->wide.kTotal = (uint32_t)v.totK;
-            // conjugation flags follow the operands into their kernel roles (kernel-A is the user's B when swapped)
-            const bool cA = desc->A.op == CUTENSOR_OP_CONJ, cB = desc->B.op == CUTENSOR_OP_CONJ;
-            pl->wide.conjA = v.swapped ? cB : cA;
-            pl->wide.conjB = v.swapped ? cA : cB;
-            pl->wide.conjC = desc->C.op == CUTENSOR_OP_CONJ;
-            // the table goes to device memory with the first cutensorContract: planning needs no GPU (and a plan that is never
-            // executed allocates nothing)
-            pl->wideTab = tab;
-            if (pl->wideTab.empty()) pl->wideTab.push_back(WideMode{make_fastdiv(1), 0, 0, 0, 0});
-            // The table goes to device memory HERE when the handle has a device — on the handle's device, outside any stream
-            // capture, so that cutensorContract neither allocates nor synchronises (it may be called while a graph is being
-            // captured).  Handles without a device (plan-only, the CPU tests) keep the host copy; a plan that one of those hands
-            // to a process with a GPU uploads at first execution.
-            if (handle->haveDevice) {
-                int prev = -1;
-                void* dev = nullptr;
-                const size_t bytes = pl->wideTab.size() * sizeof(WideMode);
-                const bool switched = hipGetDevice(&prev) == hipSuccess && prev != handle->device && hipSetDevice(handle->device) == hipSuccess;
-                if (hipMalloc(&dev, bytes) == hipSuccess && hipMemcpy(dev, pl->wideTab.data(), bytes, hipMemcpyHostToDevice) == hipSuccess)
-                    pl->wide.modes = static_cast<const WideMode*>(dev);
-                else {
-                    (void)hipGetLastError();
-                    if (dev) (void)hipFree(dev);
-                }
-                if (switched) (void)hipSetDevice(prev);
-            }
-            pl->choice = ContractionChoice{};
-            pl->choice.kernel = -2;
-            pl->requiredWorkspace = 0;
-            CT_LOG("plan: contraction with %u output + %u contracted unfusable modes -> mode-table kernel", pl->wide.nOut, pl->wide.nK);
-            *plan = owner.release();
-            return CUTENSOR_STATUS_SUCCESS;
-        }
-        const bool mfmaPath = pl->view.dtype == HIP_R_32F && !pl->accumulate64;
-        const bool h16Path = !mfmaPath && !pl->accumulate64 && desc->scalarType == HIP_R_32F &&
-                             (pl->view.dtype == HIP_R_16BF || pl->view.dtype == HIP_R_16F);
-        // general MFMA family: 16-bit shapes the aligned kernels refuse, fp64 (double scalars), complex (complex scalars)
-        const bool genPath = h16Path || (pl->view.dtype == HIP_R_64F && desc->scalarType == HIP_R_64F) ||
-                             (pl->view.dtype == HIP_C_32F && desc->scalarType == HIP_C_32F && !pl->accumulate64) ||
-                             (pl->view.dtype == HIP_C_64F && desc->scalarType == HIP_C_64F);
-        ContractionChoice pick;   // kernel = -1: simple kernel
-        std::vector<ContractionChoice> ch;
-        if (mfmaPath) ch = rank_contraction_choices(pl->view, workspaceSizeLimit, handle->numCUs, pr.operandsStreamed != 0);
-        else if (h16Path && !(CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") && CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN")[0] == 'f'))   // "force" (measurement): the general family also where the aligned 16-bit kernels apply
-            ch = rank_h16_choices(pl->view, workspaceSizeLimit, handle->numCUs);
-        double tDirect32 = (mfmaPath && desc->scalarType == HIP_R_32F && (int)pr.algo < 0 && pr.kernelRank == 0 && !ctamd_research_env("CUTENSOR_AMD_KORDER"))
-                               ? f32_direct_estimate_us(pl->view, ch) : 0.0;
-        if (mfmaPath) {
-            // a reduced-precision compute descriptor: the bf16 / fp16-rate kernels when the model (or CUTENSOR_AMD_F32X=force) says so.
-            // They take the operands as they lie (no repack pre-pass); a caller who names a candidate addresses the fp32 list as ever.
-            const int xe = f32x_elem_of(*desc);
-            ContractionChoice gx;
-            std::string note;
-            const bool explicitPickX = (int)pr.algo >= 0 || pr.kernelRank > 0 || pr.algo == CUTENSOR_ALGO_DEFAULT_PATIENT || pr.autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL;
-            if (xe >= 0 && f32x_decide(pl->view, xe, workspaceSizeLimit, handle->numCUs, explicitPickX, ch, gx, note)) {
-                ch.assign(1, gx);
-                tDirect32 = 0.0;
-            }
-            if (xe >= 0 && !note.empty()) CT_LOG("plan: fp32 contraction, compute descriptor %s: %s", xe == GEN_F32_F16 ? "16F" : xe == GEN_F32_BF16 ? "16BF" : "TF32", note.c_str());
-        }
-        if ((pl->view.dtype == HIP_R_64F || pl->view.dtype == HIP_C_32F) && desc->scalarType == pl->view.dtype && genPath && ch.empty()) {   // fp64 / complex64 on element gathers (plan_repack)
-            ContractionChoice g64;
-            if (pick_gen_choice(pl->view, workspaceSizeLimit, handle->numCUs, g64)) tDirect32 = f64_direct_estimate_us(pl->view, g64);
-        }
-        if (((h16Path && (ch.empty() || h16_sweep_waste(pl->view)) && !CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") && !CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES")) || tDirect32 > 0.0) &&
-            (int)pr.algo < 0 && pr.kernelRank == 0 &&                       // (a caller who names a candidate gets that candidate)
-            !(CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") && CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK")[0] == '0')) {
-            // the LDS-DMA kernels refuse the operands as they lie (or would spend most of every K-tile on the padding of a short ragged
-            // contracted mode): copy them into packed temporaries first when that pays (plan_repack)
-            RepackSplit rs;
-            if (plan_repack(handle, *desc, pl->view, workspaceSizeLimit, tDirect32 > 0.0 ? tDirect32 : ch.empty() ? -1.0 : ch[0].estimateUs, rs)) {
-                const uint64_t offB = (rs.bytesA + 255) & ~255ull, offW = offB + ((rs.bytesB + 255) & ~255ull);
-                cutensorPlan_t pi = nullptr, pa = nullptr, pb = nullptr;
-                {
-                    RepackScope scope;
-                    st = cutensorCreatePlan(handle, &pi, &rs.inner, pref, workspaceSizeLimit - offW);
-                }
-                if (st == CUTENSOR_STATUS_SUCCESS && rs.hasA) st = cutensorCreatePlan(handle, &pa, &rs.permA, pref, 0);
-                if (st == CUTENSOR_STATUS_SUCCESS && rs.hasB) st = cutensorCreatePlan(handle, &pb, &rs.permB, pref, 0);
-                if (st == CUTENSOR_STATUS_SUCCESS && pi->choice.family == (mfmaPath ? 0 : h16Path ? 1 : 2) && pi->sub1 == nullptr) {
-                    pl->sub1 = pi; pl->loneA = pa; pl->loneB = pb;
-                    pl->loneBytesA = rs.bytesA; pl->loneBytesB = rs.bytesB;
-                    pl->choice = ContractionChoice{};
-                    pl->choice.kernel = -4;
-                    pl->requiredWorkspace = offW + pi->requiredWorkspace;
-                    CT_LOG("plan: 16-bit contraction whose operands the LDS-DMA kernels cannot stage -> %s%scopied into packed temporaries first (%llu + %llu bytes), then the contraction",
-                           pa ? "A " : "", pb ? "B " : "", (unsigned long long)rs.bytesA, (unsigned long long)rs.bytesB);
-                    if (memoable && !t_inRepack) memo_insert(handle, mkey, mhash, *pl);
-                    *plan = owner.release();
-                    return CUTENSOR_STATUS_SUCCESS;
-                }
-                delete pi; delete pa; delete pb;                            // (the copies or the inner plan refused: the general family takes the problem as it is)
-                st = CUTENSOR_STATUS_SUCCESS;
-            }
-        }
-        if (ch.empty() && genPath && !(CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") && CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN")[0] == '0')) {
-            ContractionChoice g;
-            if (pick_gen_choice(pl->view, workspaceSizeLimit, handle->numCUs, g)) ch.push_back(g);
-        }
-        if (!ch.empty()) {
-            size_t idx = 0;
-            // (a plan made under the "operands are streamed" preference neither reads nor feeds the per-problem cache: the cache is keyed by
-            // the problem alone, and its entry belongs to the default policy)
-            const bool useCache = handle->planCacheCapacity > 0 && pr.cacheMode != CUTENSOR_CACHE_MODE_NONE && pr.operandsStreamed == 0;
-            const bool explicitPick = (int)pr.algo >= 0 || pr.kernelRank > 0;   // the caller names a candidate: the cache has no say
-            const bool incremental = useCache && !explicitPick && pr.autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL;
-            const bool patient = pr.algo == CUTENSOR_ALGO_DEFAULT_PATIENT;
-            bool needKey = incremental || (useCache && patient);
-            if (useCache && !explicitPick && !needKey) {
-                std::lock_guard<std::mutex> g(handle->mtx);
-                needKey = !handle->planCache.empty();
-            }
-            const std::string key = needKey ? problem_key(*desc) : std::string();   // the string form is what the cache FILE holds
-            bool decided = false;
-            // incremental autotuning (contraction_plan_cache.cu:215-237): the first INCREMENTAL_COUNT plans of a problem
-            // are trials of candidates 0, 1, ... (timed by cutensorContract: the best of a trial plan's first few executions);
-            // after that — and for every plan without the autotune mode — the cache answers with the fastest candidate
-            // measured so far.  (The sample's loop is count + 1 rounds of which the last must hit the cache, :262.)
-            if (incremental) {
-                resolve_pending_measurements(handle);
-                std::lock_guard<std::mutex> g(handle->mtx);
-                auto tit = handle->tuning.find(key);
-                if (tit == handle->tuning.end() && handle->tuning.size() < std::max<size_t>(handle->planCacheCapacity, 1))
-                    tit = handle->tuning.emplace(key, cutensorHandle::TuneState{}).first;   // bounded like the cache itself
-                if (tit != handle->tuning.end()) {
-                    cutensorHandle::TuneState& t = tit->second;
-                    const int limit = std::min<int>(std::max<int32_t>(pr.incrementalCount, 1), (int)ch.size());
-                    if (t.next < limit) {
-                        idx = (size_t)t.next++;
-                        pl->tuneKey = key;
-                        decided = true;
-                    }
-                }
-            }
-            if (!decided && useCache && !explicitPick) {
-                std::lock_guard<std::mutex> g(handle->mtx);
-                auto it = needKey ? handle->planCache.find(key) : handle->planCache.end();
-                if (it != handle->planCache.end())
-                    for (size_t i = 0; i < ch.size(); ++i)
-                        if (ch[i].kernel == it->second.kernel && ch[i].splitK == it->second.splitK) { idx = i; decided = true; break; }
-            }
-            if (!decided) {
-                if ((int)pr.algo >= 0) idx = std::min<size_t>((size_t)pr.algo, ch.size() - 1);
-                else if (pr.kernelRank > 0) idx = std::min<size_t>((size_t)pr.kernelRank, ch.size() - 1);
-                else if (patient) idx = (size_t)autotune_contraction(handle, *desc, pl->view, ch);
-                if (const char* f = ctamd_research_env("CUTENSOR_AMD_FORCE")) {   // "kernel:splitK" experiment knob
-                    int fk = -1; unsigned fs = 1;
-                    if (std::sscanf(f, "%d:%u", &fk, &fs) >= 1)
-                        for (size_t i = 0; i < ch.size(); ++i)
-                            if (ch[i].kernel == fk && ch[i].splitK == fs) { idx = i; break; }
-                }
-                if (useCache && patient) {
-                    std::lock_guard<std::mutex> g(handle->mtx);
-                    if (handle->planCache.size() < handle->planCacheCapacity) {
-                        handle->planCache[key] = PlanCacheEntry{key, ch[idx].kernel, ch[idx].splitK};
-                        handle->planMemo.clear();   // a DEFAULT prototype memoised earlier must not shadow the measured choice
-                    }
-                }
-            }
-            pick = ch[idx];
-        }
-        pl->choice = pick;
-        fill_gett_params(pl->view, pick, pl->gett, pl->skr);
-        {   // conjugation follows the operands into their kernel roles (kernel-A is the user's B when swapped)
-            const bool cA = desc->A.op == CUTENSOR_OP_CONJ, cB = desc->B.op == CUTENSOR_OP_CONJ;
-            pl->gett.conjA = pl->view.swapped ? cB : cA;
-            pl->gett.conjB = pl->view.swapped ? cA : cB;
-            pl->gett.conjC = desc->C.op == CUTENSOR_OP_CONJ;
-        }
-        pl->requiredWorkspace = pick.workspace;
-        // Per-XCD K split (one output tile, split-K over whole XCD rows): see calibrate_xcd_split
-        if (mfmaPath && pick.kernel >= 0 && pick.family == 0 && pick.splitK >= 64 && pl->view.totL == 1 && pl->gett.tilesM * pl->gett.tilesN == 1) {
-            int cnt = 0;
-            const GettKernelInfo* tabf = gett_f32_kernels(&cnt);
-            const char* env = ctamd_research_env("CUTENSOR_AMD_XCD_BALANCE");
-            // opt-in: on the parts measured the clocks differ by +-1.5 %, below the 1-tile-in-32 (3 %) granularity
-            // of the headline split, so the apportionment comes out uniform
-            if (env && env[0] == '1' && tabf[pick.kernel].fragPartials && !tabf[pick.kernel].ablation)
-                pl->gett.xcdTiles = calibrate_xcd_split(handle, *desc, *pl);
-        }
-        // In-launch fold of the split-K partials: only when every workgroup of the launch owns a CU of its own
-        // (they wait for each other) and the output is a plain matrix; otherwise the fold is a second kernel.
-        if (mfmaPath && pick.kernel >= 0 && pick.family == 0 && pick.splitK > 1) {
-            int cnt = 0;
-            const GettKernelInfo* tabf = gett_f32_kernels(&cnt);
-            const char* env = CTAMD_HOOK_ENV("CUTENSOR_AMD_FUSED_FOLD");
-            const bool allowed = env && env[0] == '1';   // opt-in: measured slower than the two-kernel fold
-            if (allowed && tabf[pick.kernel].fragPartials && !tabf[pick.kernel].ablation && pl->gett.nBlocks <= (uint32_t)handle->numCUs &&
-                pl->view.totL == 1 && pl->view.M.size() <= 1 && pl->view.N.size() <= 1) {
-                std::lock_guard<std::mutex> g(handle->mtx);
-                if (handle->syncPool == nullptr) {
-                    void* ptr = nullptr;
-                    const size_t bytes = (size_t)cutensorHandle::kSyncSlots * 64;
-                    if (hipMalloc(&ptr, bytes) == hipSuccess && hipMemset(ptr, 0, bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess)
-                        handle->syncPool = static_cast<uint32_t*>(ptr);
-                    else
-                        (void)hipGetLastError();
-                }
-                pl->fusedFold = handle->syncPool != nullptr;
-            }
-        }
-        pl->requiredWorkspace = pick.workspace;
-        if (log_level() > 0) {
-            int count = 0;
-            const GettKernelInfo* tab = gett_f32_kernels(&count);
-            if (pick.family == 2) {
-                int gc = 0;
-                const GettKernelInfo* gt = gett_gen_kernels(&gc);
-                CT_LOG("plan: contraction (general MFMA family) dtype=%d L=%llu M=%llu N=%llu K=%llu swapped=%d -> gen kernel %d (%dx%dx%d orientA=%d orientB=%d V=%d) splitK=%u",
-                       (int)pl->view.dtype, (unsigned long long)pl->view.totL, (unsigned long long)pl->view.totM, (unsigned long long)pl->view.totN,
-                       (unsigned long long)pl->view.totK, (int)pl->view.swapped, pick.kernel, gt[pick.kernel].bm, gt[pick.kernel].bn, gt[pick.kernel].bk,
-                       gt[pick.kernel].layA, gt[pick.kernel].layB, gt[pick.kernel].vec, pick.splitK);
-            } else if (pick.family == 1)
-                CT_LOG("plan: contraction (16-bit MFMA) L=%llu M=%llu N=%llu K=%llu layA=%d layB=%d swapped=%d -> h16 kernel %d",
-                       (unsigned long long)pl->view.totL, (unsigned long long)pl->view.totM, (unsigned long long)pl->view.totN,
-                       (unsigned long long)pl->view.totK, pl->view.layA, pl->view.layB, (int)pl->view.swapped, pick.kernel);
-            else if (pick.kernel >= 0)
-                CT_LOG("plan: contraction L=%llu M=%llu N=%llu K=%llu layA=%d layB=%d swapped=%d -> kernel %d (%dx%dx%d) splitK=%u ws=%llu est=%.1fus",
-                       (unsigned long long)pl->view.totL, (unsigned long long)pl->view.totM, (unsigned long long)pl->view.totN,
-                       (unsigned long long)pl->view.totK, pl->view.layA, pl->view.layB, (int)pl->view.swapped, pick.kernel,
-                       tab[pick.kernel].bm, tab[pick.kernel].bn, tab[pick.kernel].bk, pick.splitK,
-                       (unsigned long long)pick.workspace, pick.estimateUs);
-            else
-                CT_LOG("plan: contraction -> simple kernel (dtype %d)", (int)pl->view.dtype);
-        }
-    } else if (desc->kind == OpKind::Reduction) {
-        st = plan_reduction(*desc, workspaceSizeLimit, handle->numCUs, pl->red, &why);
-        if (st != CUTENSOR_STATUS_SUCCESS) { return st; }
-        pl->requiredWorkspace = pl->red.workspace;
-        CT_LOG("plan: reduction variant=%d kept=%u red=%u splitR=%u perm=%d", pl->red.variant, pl->red.p.kept.total,
-               pl->red.p.red.total, pl->red.p.splitR, (int)pl->red.isPermutation);
-    } else if (desc->kind == OpKind::ElementwiseTrinary) {
-        st = plan_elementwise_trinary(*desc, pl->ew3, &why);
-        if (st != CUTENSOR_STATUS_SUCCESS) { return st; }
-        pl->alignB3 = desc->B.desc.alignment;
-        pl->requiredWorkspace = 0;
-        CT_LOG("plan: elementwise trinary passes=%d swapAB=%d bothPermuted=%d variant(last)=%d", pl->ew3.twoPass ? 2 : 1, (int)pl->ew3.swapAB,
-               (int)pl->ew3.bothPermuted, pl->ew3.last.variant);
-    } else if (desc->kind == OpKind::Permutation && (!desc->padLeft.empty() || !desc->padRight.empty())) {
-        // The output buffer is the packed tensor of extents e + padLeft + padRight (the sample sizes it that way,
-        // elementwise_permute_padding.cu:101-103); the descriptor carries the unpadded extents.
-        const size_t nm = desc->D.modes.size();
-        std::vector<int64_t> packed(nm), padded(nm);
-        int64_t accU = 1, accP = 1, offset = 0;
-        bool isPacked = true;
-        for (size_t i = 0; i < nm; ++i) {
-            const int64_t l = desc->padLeft.empty() ? 0 : desc->padLeft[i], r = desc->padRight.empty() ? 0 : desc->padRight[i];
-            packed[i] = accU; padded[i] = accP;
-            isPacked = isPacked && (desc->D.desc.extent[i] == 1 || desc->D.desc.stride[i] == accU);
-            offset += l * accP;
-            accU *= desc->D.desc.extent[i];
-            accP *= desc->D.desc.extent[i] + l + r;
-        }
-        if (!isPacked) { CT_LOG("cutensorCreatePlan: padding needs a packed output descriptor"); return CUTENSOR_STATUS_NOT_SUPPORTED; }
-        cutensorOperationDescriptor inner = *desc;
-        inner.D.desc.stride = padded;
-        // the interior starts `offset` elements into the buffer: keep the 16-byte-lane variants only if that is lane-aligned
-        const int64_t lane = 16 / (int64_t)dtype_size(desc->D.desc.dtype);
-        if (offset % lane != 0) inner.D.desc.alignment = (uint32_t)dtype_size(desc->D.desc.dtype);
-        st = plan_elementwise(inner, pl->ew, &why);
-        if (st != CUTENSOR_STATUS_SUCCESS) { return st; }
-        pl->padFillElems = (uint64_t)accP;
-        pl->padOffsetElems = offset;
-        pl->padValue = desc->padValue;
-        pl->requiredWorkspace = 0;
-        CT_LOG("plan: padded permutation variant=%d fill=%llu elems offset=%lld", pl->ew.variant, (unsigned long long)pl->padFillElems, (long long)offset);
-    } else {
-        st = plan_elementwise(*desc, pl->ew, &why);
-        if (st != CUTENSOR_STATUS_SUCCESS) { return st; }
-        pl->requiredWorkspace = 0;
-        CT_LOG("plan: elementwise variant=%d E0=%u E1=%u rest=%u blocks=%u", pl->ew.variant, pl->ew.p.E0, pl->ew.p.E1,
-               pl->ew.p.rest.total, pl->ew.p.nBlocks);
-    }
-    if (memoable) memo_insert(handle, mkey, mhash, *pl);
-    *plan = owner.release();
+    const cutensorStatus_t st = build_plan(PlanRequest{handle, *desc, pref, pr, workspaceSizeLimit}, *pl);
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    if (memoable) memo_insert(handle, mkey, mhash, *pl);   // (only plans that own nothing a clone could not copy: plan_is_prototype)
+    *plan = pl.release();
     return CUTENSOR_STATUS_SUCCESS;
 } CTAMD_API_CATCH
 
-cutensorPlan::~cutensorPlan() {
-    delete sub1;
-    delete sub2;
-    delete loneA;
-    delete loneB;
-    if (wide.modes != nullptr) (void)hipFree(const_cast<ctamd::WideMode*>(wide.modes));
-}
 
 cutensorStatus_t cutensorDestroyPlan(cutensorPlan_t plan) try {
     delete plan;
@@ -1881,6 +1868,160 @@ cutensorStatus_t cutensorPlanGetAttribute(const cutensorHandle_t handle, const c
 } CTAMD_API_CATCH
 
 // ---- execution -----------------------------------------------------------------------------------
+// alpha and beta of a call as the kernels take them, and 1 / 0 in a plan's scalar type ({re, im} pairs: also the complex ones)
+struct CallScalars { double a, b, aIm, bIm; };
+static const void* scalar_constant(hipDataType scalarType, bool one) {
+    static const float f[2][2] = {{0.f, 0.f}, {1.f, 0.f}};
+    static const double d[2][2] = {{0.0, 0.0}, {1.0, 0.0}};
+    return (scalarType == HIP_R_64F || scalarType == HIP_C_64F) ? static_cast<const void*>(d[one]) : static_cast<const void*>(f[one]);
+}
+// LoneReduce / Repack plans: the first step of an operand is a reduction over its lone modes (split_lone_modes) or a permuted copy
+// (plan_repack) into its packed temporary at the head of the workspace; then the inner contraction runs on the temporaries
+static cutensorStatus_t run_two_step(const cutensorHandle_t handle, const cutensorPlan& plan, const void* alpha, const void* A, const void* B,
+                                     const void* beta, const void* C, void* D, void* workspace, uint64_t workspaceSize, cudaStream_t stream) {
+    if (!plan.sub1) return CUTENSOR_STATUS_INVALID_VALUE;
+    const TwoStepLayout lay(plan.loneBytesA, plan.loneBytesB);
+    char* ws = static_cast<char*>(workspace);
+    const void* one = scalar_constant(plan.scalarType, true);
+    const void* zero = scalar_constant(plan.scalarType, false);
+    // fp16 temporaries (float scalars): scaled down by exact powers of two, alpha scaled up by their product (loneShiftA: internal.hpp)
+    const float scaleA = std::ldexp(1.f, -plan.loneShiftA), scaleB = std::ldexp(1.f, -plan.loneShiftB);
+    const bool scaled = plan.loneShiftA + plan.loneShiftB > 0;
+    const float alphaScaled = scaled ? *static_cast<const float*>(alpha) * std::ldexp(1.f, plan.loneShiftA + plan.loneShiftB) : 0.f;
+    auto first_step = [&](const SubPlan& step, const float& scale, const void* X, char* T) {
+        return plan.planKind == PlanKind::Repack ? cutensorPermute(handle, step.get(), one, X, T, stream)
+                                                 : cutensorReduce(handle, step.get(), scaled ? &scale : one, X, zero, T, T, ws + lay.offW, workspaceSize - lay.offW, stream);
+    };
+    cutensorStatus_t st = CUTENSOR_STATUS_SUCCESS;
+    if (plan.loneA) { st = first_step(plan.loneA, scaleA, A, ws); A = ws; }
+    if (st == CUTENSOR_STATUS_SUCCESS && plan.loneB) { st = first_step(plan.loneB, scaleB, B, ws + lay.offB); B = ws + lay.offB; }
+    if (st != CUTENSOR_STATUS_SUCCESS) return st;
+    return cutensorContract(handle, plan.sub1.get(), scaled ? &alphaScaled : alpha, A, B, beta, C, D, ws + lay.offW, workspaceSize - lay.offW, stream);
+}
+// Peeled plans: every index combination of the peeled modes is one launch of the inner plan on offset operands; a combination whose
+// contracted indices are all zero writes its region of D first (caller's beta, caller's C), the others accumulate into it
+static cutensorStatus_t run_peeled(const cutensorHandle_t handle, const cutensorPlan& plan, const void* alpha, const void* A, const void* B,
+                                   const void* beta, const void* C, void* D, void* workspace, uint64_t workspaceSize, cudaStream_t stream) {
+    if (!plan.sub1) return CUTENSOR_STATUS_INVALID_VALUE;
+    const int64_t es = (int64_t)dtype_size(plan.dtype);
+    const void* one = scalar_constant(plan.scalarType, true);
+    const size_t n = plan.peel.size();
+    std::vector<int64_t> digit(n, 0);
+    for (;;) {
+        int64_t oA = 0, oB = 0, oC = 0, oD = 0;
+        bool first = true;
+        for (size_t i = 0; i < n; ++i) {
+            const PeelMode& pm = plan.peel[i];
+            oA += digit[i] * pm.sA; oB += digit[i] * pm.sB; oC += digit[i] * pm.sC; oD += digit[i] * pm.sD;
+            if (pm.contracted && digit[i] != 0) first = false;
+        }
+        char* d = static_cast<char*>(D) + oD * es;
+        const char* c = first ? (C ? static_cast<const char*>(C) + oC * es : nullptr) : d;
+        // accumulate launches read D in D's own layout (sub2, when the caller's C is laid out differently or conjugated)
+        const cutensorStatus_t st = cutensorContract(handle, (!first && plan.sub2) ? plan.sub2.get() : plan.sub1.get(), alpha, static_cast<const char*>(A) + oA * es,
+                                                     static_cast<const char*>(B) + oB * es, first ? beta : one, c, d, workspace, workspaceSize, stream);
+        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        size_t i = 0;
+        for (; i < n; ++i) {
+            if (++digit[i] < plan.peel[i].extent) break;
+            digit[i] = 0;
+        }
+        if (i == n) return CUTENSOR_STATUS_SUCCESS;
+    }
+}
+// Per-kernel timing (ctamdProfileBegin): an event pair around the GETT launch of a tiled plan, kept by the handle
+struct ProfiledLaunch {
+    cutensorHandle* handle;
+    hipStream_t stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ProfiledLaunch(cutensorHandle* h, hipStream_t s) : handle(h), stream(s) {
+        if (h->prof.enabled.load(std::memory_order_relaxed) && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
+            (void)hipEventRecord(e0, stream);
+    }
+    void end() {
+        if (!e0 || !e1) return;
+        (void)hipEventRecord(e1, stream);
+        std::lock_guard<std::mutex> g(handle->prof.mtx);
+        handle->prof.events.emplace_back(e0, e1);
+    }
+};
+static bool mode_table_on_device(const cutensorHandle_t handle, cutensorPlan& plan) {
+    if (plan.wideDev) return true;
+    std::lock_guard<std::mutex> g(handle->mtx);
+    if (!plan.wideDev) plan.wideDev = upload_mode_table(plan.wideTab);
+    return plan.wideDev != nullptr;
+}
+static hipError_t launch_mode_table(const cutensorPlan& plan, const GettParams& p, const CallScalars& s, hipStream_t stream) {
+    WideParams w = plan.wide;
+    w.modes = plan.wideDev.get();
+    w.A = p.A; w.B = p.B; w.C = p.C; w.D = p.D;
+    w.alpha = p.alpha; w.beta = p.beta; w.alpha64 = s.a; w.beta64 = s.b;
+    w.alphaIm = s.aIm; w.betaIm = s.bIm;
+    g_launchCounts[1].fetch_add(1, std::memory_order_relaxed);
+    return launch_gett_wide(w, (int)plan.dtype, plan.accumulate64, stream);
+}
+// Strip plan (ContractionChoice::stripKernel): the interior's whole tiles on kernel `ki`, then the two edge strips (rows past mInt x all
+// columns, rows below mInt x columns past nInt) as ONE launch of the 64 x 64 tile `ks` with two tile rectangles
+static hipError_t launch_strip_plan(const ContractionChoice& c, const GettKernelInfo& ki, const GettKernelInfo& ks, const GettParams& p, hipStream_t stream) {
+    const uint32_t mInt = c.mInt, nInt = c.nInt, Mt = p.gM.total, Nt = p.gN.total, Lt = p.gL.total;
+    GettParams q = p;
+    q.tilesM = mInt / (uint32_t)ki.bm; q.tilesN = nInt / (uint32_t)ki.bn;
+    q.nBlocks = q.tilesM * q.tilesN * Lt;
+    const hipError_t err = ki.launch(q, stream);
+    GettParams s2 = p;
+    s2.mOrg = mInt; s2.nOrg = 0;
+    s2.tilesM = (Mt - mInt + (uint32_t)ks.bm - 1u) / (uint32_t)ks.bm; s2.tilesN = (Nt + (uint32_t)ks.bn - 1u) / (uint32_t)ks.bn;
+    s2.mOrg2 = 0; s2.nOrg2 = nInt;
+    s2.tilesM2 = (mInt + (uint32_t)ks.bm - 1u) / (uint32_t)ks.bm; s2.tilesN2 = (Nt - nInt + (uint32_t)ks.bn - 1u) / (uint32_t)ks.bn;
+    if (s2.tilesM * s2.tilesN == 0u) {     // no rows past the interior: the column strip is the only rectangle
+        s2.mOrg = s2.mOrg2; s2.nOrg = s2.nOrg2; s2.tilesM = s2.tilesM2; s2.tilesN = s2.tilesN2;
+        s2.tilesM2 = s2.tilesN2 = 0;
+    }
+    s2.nBlocks = (s2.tilesM * s2.tilesN + s2.tilesM2 * s2.tilesN2) * Lt;
+    return (err == hipSuccess && s2.nBlocks > 0u) ? ks.launch(s2, stream) : err;
+}
+// Tiled plans: the GETT launch of the plan's kernel and, for split-K, the fold that matches the kernel's partials
+static hipError_t launch_tiled(const cutensorHandle_t handle, const cutensorPlan& plan, GettParams& p, const CallScalars& s, void* workspace, hipStream_t stream) {
+    const ContractionChoice& c = plan.choice;
+    int count = 0;
+    const GettKernelInfo* tab = kernel_table(c.family, &count);
+    g_launchCounts[2 + c.family].fetch_add(1, std::memory_order_relaxed);
+    p.partial = (c.splitK > 1) ? static_cast<float*>(workspace) : nullptr;
+    int launchKernel = c.kernel;
+    if (c.family == 0) {
+        static const int policy = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_PARTIAL_STORE"); return e ? (e[0] == 'p' ? 1 : e[0] == 'n' ? 2 : e[0] == 's' ? 3 : 0) : 0; }();   // hooks flavour; 's': the row epilogue skips its stores (timing only)
+        p.partialPolicy = policy;
+        if (plan.fusedFold) {
+            uint32_t slot;
+            {
+                std::lock_guard<std::mutex> g(handle->mtx);
+                slot = handle->syncNext++ % cutensorHandle::kSyncSlots;
+            }
+            p.sync = handle->syncPool + (size_t)slot * 16;
+        }
+    } else if (c.family == 1) {
+        // beta is known only now.  The persistent 16-bit kernel (H16_W4P) streams its tiles with beta != 0 too since round 6 (C joins the
+        // accumulators through the idle row image: gett_h16p.hip) — when C has the 16-byte lanes of D (its fastest N mode contiguous).
+        // Any other C sends every tile through the ring-resident epilogue, where the kernel is slower than its one-tile twin (H16_W4X:
+        // same tile, same arguments, same workspace; profiles/r05r_h16p_beta.jsonl): the twin is launched then
+        // (CUTENSOR_AMD_H16_WAVES=4p names the kernel for every call: the tests of that path)
+        static const bool persistentForced = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") != nullptr && h16_waves_variant() == H16_W4P;
+        if (tab[launchKernel].variant == H16_W4P && s.b != 0.0 && p.cStrideN[0] != 1 && !persistentForced)
+            launchKernel = h16_entry(H16_W4X, launchKernel - H16_W4P);
+        g_lastH16Kernel.store(launchKernel, std::memory_order_relaxed);
+    }
+    ProfiledLaunch prof(handle, stream);
+    hipError_t err = (c.family == 1 && c.stripKernel >= 0 && c.stripKernel < count) ? launch_strip_plan(c, tab[launchKernel], tab[c.stripKernel], p, stream)
+                                                                                    : tab[launchKernel].launch(p, stream);
+    prof.end();
+    if (err != hipSuccess || c.splitK <= 1 || (c.family == 0 && (plan.fusedFold || handle->skipFold.load(std::memory_order_relaxed)))) return err;
+    SplitKReduceParams r = plan.skr;
+    r.partial = static_cast<float*>(workspace);
+    r.C = p.C; r.D = p.D; r.alpha = p.alpha; r.beta = p.beta;
+    r.alpha64 = s.a; r.beta64 = s.b; r.alphaIm = s.aIm; r.betaIm = s.bIm; r.conjC = p.conjC;
+    return launch_splitk_fold(c.family, tab[c.kernel], r, stream);
+}
+
 // contraction.cu:261-265, einsum.cu:334-338
 cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorPlan_t plan, const void* alpha,
                                   const void* A, const void* B, const void* beta, const void* C, void* D,
@@ -1888,91 +2029,32 @@ cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorP
     if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
     if (plan == nullptr || plan->kind != OpKind::Contraction) return CUTENSOR_STATUS_INVALID_VALUE;
     if (alpha == nullptr || beta == nullptr || A == nullptr || B == nullptr || D == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-    const double a = scalar_as_double(alpha, plan->scalarType), b = scalar_as_double(beta, plan->scalarType);
-    const double aIm = scalar_imag(alpha, plan->scalarType), bIm = scalar_imag(beta, plan->scalarType);
-    const bool betaZero = (b == 0.0 && bIm == 0.0);
+    const CallScalars s{scalar_as_double(alpha, plan->scalarType), scalar_as_double(beta, plan->scalarType), scalar_imag(alpha, plan->scalarType),
+                        scalar_imag(beta, plan->scalarType)};
+    const bool betaZero = (s.b == 0.0 && s.bIm == 0.0);
     if (!betaZero && C == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
     if (misaligned(A, plan->alignA) || misaligned(B, plan->alignB) || misaligned(D, plan->alignD) ||
         (!betaZero && misaligned(C, plan->alignC)))
         return CUTENSOR_STATUS_INVALID_VALUE;
     if (plan->requiredWorkspace > 0 && (workspace == nullptr || workspaceSize < plan->requiredWorkspace))
         return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;
-
-    if (plan->choice.kernel == -4) {
-        // a mode that one input alone carries (split_lone_modes): reduce that input over it into its temporary, contract the temporaries
-        if (plan->sub1 == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-        const uint64_t offB = (plan->loneBytesA + 255) & ~255ull, offW = offB + ((plan->loneBytesB + 255) & ~255ull);
-        char* ws = static_cast<char*>(workspace);
-        const float onef[2] = {1.f, 0.f}, zerof[2] = {0.f, 0.f};
-        const double oned[2] = {1.0, 0.0}, zerod[2] = {0.0, 0.0};
-        const bool wideScalar = plan->scalarType == HIP_R_64F || plan->scalarType == HIP_C_64F;
-        const void* one = wideScalar ? static_cast<const void*>(oned) : static_cast<const void*>(onef);
-        const void* zero = wideScalar ? static_cast<const void*>(zerod) : static_cast<const void*>(zerof);
-        const void* a = A;
-        const void* bb = B;
-        // fp16 temporaries (float scalars): scaled down by exact powers of two, alpha scaled up by their product (loneShiftA: internal.hpp)
-        const float scaleA = std::ldexp(1.f, -plan->loneShiftA), scaleB = std::ldexp(1.f, -plan->loneShiftB);
-        const bool scaled = plan->loneShiftA + plan->loneShiftB > 0;
-        const float alphaScaled = scaled ? *static_cast<const float*>(alpha) * std::ldexp(1.f, plan->loneShiftA + plan->loneShiftB) : 0.f;
-        cutensorStatus_t st = CUTENSOR_STATUS_SUCCESS;
-        // (the first step of an operand is a reduction over its lone modes, or — plan_repack — a permuted copy into a packed temporary)
-        if (plan->loneA) {
-            st = plan->loneA->kind == OpKind::Permutation ? cutensorPermute(handle, plan->loneA, one, A, ws, stream)
-                                                         : cutensorReduce(handle, plan->loneA, scaled ? &scaleA : one, A, zero, ws, ws, ws + offW, workspaceSize - offW, stream);
-            a = ws;
-        }
-        if (st == CUTENSOR_STATUS_SUCCESS && plan->loneB) {
-            st = plan->loneB->kind == OpKind::Permutation ? cutensorPermute(handle, plan->loneB, one, B, ws + offB, stream)
-                                                         : cutensorReduce(handle, plan->loneB, scaled ? &scaleB : one, B, zero, ws + offB, ws + offB, ws + offW, workspaceSize - offW, stream);
-            bb = ws + offB;
-        }
-        if (st != CUTENSOR_STATUS_SUCCESS) return st;
-        return cutensorContract(handle, plan->sub1, scaled ? &alphaScaled : alpha, a, bb, beta, C, D, ws + offW, workspaceSize - offW, stream);
+    switch (plan->planKind) {
+        case PlanKind::LoneReduce:
+        case PlanKind::Repack: return run_two_step(handle, *plan, alpha, A, B, beta, C, D, workspace, workspaceSize, stream);
+        case PlanKind::Peeled: return run_peeled(handle, *plan, alpha, A, B, beta, C, D, workspace, workspaceSize, stream);
+        case PlanKind::ModeTable:   // first execution of a plan made without a device: the mode table moves there (kept until the plan dies)
+            if (!mode_table_on_device(handle, *plan)) return CUTENSOR_STATUS_ALLOC_FAILED;
+            break;
+        default: break;
     }
-    if (plan->choice.kernel == -3) {
-        // peeled contraction: every index combination of the peeled modes is one launch of the inner plan on offset operands;
-        // a combination whose contracted indices are all zero writes its region of D first (caller's beta, caller's C), the
-        // others accumulate into it
-        if (plan->sub1 == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-        const size_t es = dtype_size(plan->dtype);
-        const float onef[2] = {1.f, 0.f};      // (real, imaginary): also the complex one
-        const double oned[2] = {1.0, 0.0};
-        const void* one = (plan->scalarType == HIP_R_64F || plan->scalarType == HIP_C_64F) ? static_cast<const void*>(oned) : static_cast<const void*>(onef);
-        const size_t n = plan->peel.size();
-        std::vector<int64_t> digit(n, 0);
-        for (;;) {
-            int64_t oA = 0, oB = 0, oC = 0, oD = 0;
-            bool first = true;
-            for (size_t i = 0; i < n; ++i) {
-                const PeelMode& pm = plan->peel[i];
-                oA += digit[i] * pm.sA; oB += digit[i] * pm.sB; oC += digit[i] * pm.sC; oD += digit[i] * pm.sD;
-                if (pm.contracted && digit[i] != 0) first = false;
-            }
-            char* d = static_cast<char*>(D) + oD * (int64_t)es;
-            const char* c = first ? (C ? static_cast<const char*>(C) + oC * (int64_t)es : nullptr) : d;
-            // accumulate launches read D in D's own layout (sub2, when the caller's C is laid out differently or conjugated)
-            const cutensorStatus_t st = cutensorContract(handle, (!first && plan->sub2) ? plan->sub2 : plan->sub1, alpha, static_cast<const char*>(A) + oA * (int64_t)es,
-                                                         static_cast<const char*>(B) + oB * (int64_t)es, first ? beta : one, c, d, workspace,
-                                                         workspaceSize, stream);
-            if (st != CUTENSOR_STATUS_SUCCESS) return st;
-            size_t i = 0;
-            for (; i < n; ++i) {
-                if (++digit[i] < plan->peel[i].extent) break;
-                digit[i] = 0;
-            }
-            if (i == n) break;
-        }
-        return CUTENSOR_STATUS_SUCCESS;
-    }
-
     GettParams p = plan->gett;
     p.A = plan->view.swapped ? B : A;
     p.B = plan->view.swapped ? A : B;
     p.C = (!betaZero) ? C : D;
     p.D = D;
-    p.alpha = (float)a; p.beta = (float)b;
-    p.alpha64 = a; p.beta64 = b;
-    p.alphaIm = aIm; p.betaIm = bIm;
+    p.alpha = (float)s.a; p.beta = (float)s.b;
+    p.alpha64 = s.a; p.beta64 = s.b;
+    p.alphaIm = s.aIm; p.betaIm = s.bIm;
     p.endA += (unsigned long long)(uintptr_t)p.A;   // the plan holds the operands' byte spans (fill_gett_params)
     p.endB += (unsigned long long)(uintptr_t)p.B;
     p.timing = handle->timingBuffer.load(std::memory_order_relaxed);
@@ -1991,117 +2073,12 @@ cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorP
         }
     }
     hipError_t err;
-    if (plan->choice.kernel == -2) {
-        if (plan->wide.modes == nullptr) {   // first execution: the mode table moves to the device (kept until the plan dies)
-            std::lock_guard<std::mutex> g(handle->mtx);
-            if (plan->wide.modes == nullptr) {
-                void* dev = nullptr;
-                const size_t bytes = plan->wideTab.size() * sizeof(WideMode);
-                if (hipMalloc(&dev, bytes) != hipSuccess || hipMemcpy(dev, plan->wideTab.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-                    (void)hipGetLastError();
-                    if (dev) (void)hipFree(dev);
-                    return CUTENSOR_STATUS_ALLOC_FAILED;
-                }
-                plan->wide.modes = static_cast<const WideMode*>(dev);
-            }
-        }
-        WideParams w = plan->wide;
-        w.A = p.A; w.B = p.B; w.C = p.C; w.D = D;
-        w.alpha = p.alpha; w.beta = p.beta; w.alpha64 = a; w.beta64 = b;
-        w.alphaIm = aIm; w.betaIm = bIm;
-        err = launch_gett_wide(w, (int)plan->dtype, plan->accumulate64, stream);
-        g_launchCounts[1].fetch_add(1, std::memory_order_relaxed);
-    } else if (plan->choice.kernel < 0) {
+    if (plan->planKind == PlanKind::ModeTable) err = launch_mode_table(*plan, p, s, stream);
+    else if (plan->planKind == PlanKind::Tiled) err = launch_tiled(handle, *plan, p, s, workspace, stream);
+    else {
         g_launchCounts[0].fetch_add(1, std::memory_order_relaxed);
         p.partial = nullptr;
         err = launch_gett_simple(p, (int)plan->dtype, plan->accumulate64, stream);
-    } else if (plan->choice.family == 1 || plan->choice.family == 2) {
-        int count = 0;
-        const GettKernelInfo* tab = plan->choice.family == 2 ? gett_gen_kernels(&count) : gett_h16_kernels(&count);
-        g_launchCounts[plan->choice.family == 2 ? 4 : 3].fetch_add(1, std::memory_order_relaxed);
-        p.partial = (plan->choice.splitK > 1) ? static_cast<float*>(workspace) : nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (handle->prof.enabled.load(std::memory_order_relaxed) && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
-            (void)hipEventRecord(e0, stream);
-        int launchKernel = plan->choice.kernel;
-        // beta is known only now.  The persistent 16-bit kernel (table entries 88..95) streams its tiles with beta != 0 too since round 6
-        // (C joins the accumulators through the idle row image: gett_h16p.hip) — when C has the 16-byte lanes of D (its fastest N mode
-        // contiguous).  Any other C sends every tile through the ring-resident epilogue, where the kernel is slower than its one-tile
-        // twin (48..55: same tile, same arguments, same workspace; profiles/r05r_h16p_beta.jsonl): the twin is launched then
-        // (CUTENSOR_AMD_H16_WAVES=4p names the kernel for every call: the tests of that path)
-        static const bool persistentForced = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES"); return e && e[0] == '4' && e[1] == 'p'; }();
-        if (plan->choice.family == 1 && tab[launchKernel].pf == 12 && b != 0.0 && p.cStrideN[0] != 1 && !persistentForced && launchKernel - 40 >= 0 &&
-            tab[launchKernel - 40].pf == 7)
-            launchKernel -= 40;
-        if (plan->choice.family == 1) g_lastH16Kernel.store(launchKernel, std::memory_order_relaxed);
-        if (plan->choice.family == 1 && plan->choice.stripKernel >= 0 && plan->choice.stripKernel < count) {
-            // strip plan: the interior's whole tiles on the chosen kernel, then the two edge strips (rows past mInt x all columns, rows
-            // below mInt x columns past nInt) as ONE launch of the 64 x 64 tile with two tile rectangles
-            const GettKernelInfo& ki = tab[launchKernel];
-            const GettKernelInfo& ks = tab[plan->choice.stripKernel];
-            const uint32_t mInt = plan->choice.mInt, nInt = plan->choice.nInt, Mt = p.gM.total, Nt = p.gN.total, Lt = p.gL.total;
-            GettParams q = p;
-            q.tilesM = mInt / (uint32_t)ki.bm; q.tilesN = nInt / (uint32_t)ki.bn;
-            q.nBlocks = q.tilesM * q.tilesN * Lt;
-            err = ki.launch(q, stream);
-            GettParams s2 = p;
-            s2.mOrg = mInt; s2.nOrg = 0;
-            s2.tilesM = (Mt - mInt + (uint32_t)ks.bm - 1u) / (uint32_t)ks.bm; s2.tilesN = (Nt + (uint32_t)ks.bn - 1u) / (uint32_t)ks.bn;
-            s2.mOrg2 = 0; s2.nOrg2 = nInt;
-            s2.tilesM2 = (mInt + (uint32_t)ks.bm - 1u) / (uint32_t)ks.bm; s2.tilesN2 = (Nt - nInt + (uint32_t)ks.bn - 1u) / (uint32_t)ks.bn;
-            if (s2.tilesM * s2.tilesN == 0u) {     // no rows past the interior: the column strip is the only rectangle
-                s2.mOrg = s2.mOrg2; s2.nOrg = s2.nOrg2; s2.tilesM = s2.tilesM2; s2.tilesN = s2.tilesN2;
-                s2.tilesM2 = s2.tilesN2 = 0;
-            }
-            s2.nBlocks = (s2.tilesM * s2.tilesN + s2.tilesM2 * s2.tilesN2) * Lt;
-            if (err == hipSuccess && s2.nBlocks > 0u) err = ks.launch(s2, stream);
-        } else
-        err = tab[launchKernel].launch(p, stream);
-        if (e0 && e1) {
-            (void)hipEventRecord(e1, stream);
-            std::lock_guard<std::mutex> g(handle->prof.mtx);
-            handle->prof.events.emplace_back(e0, e1);
-        }
-        if (err == hipSuccess && plan->choice.splitK > 1) {
-            SplitKReduceParams r = plan->skr;
-            r.partial = static_cast<float*>(workspace);
-            r.C = p.C; r.D = D; r.alpha = p.alpha; r.beta = p.beta;
-            r.alpha64 = a; r.beta64 = b; r.alphaIm = aIm; r.betaIm = bIm; r.conjC = p.conjC;
-            const int elem = plan->choice.family == 2 ? tab[plan->choice.kernel].elem : GEN_BF16;
-            err = !gen_elem_f32_partials(elem) ? launch_gen_splitk_reduce(r, elem, stream) : launch_splitk_reduce(r, stream);
-        }
-    } else {
-        int count = 0;
-        const GettKernelInfo* tab = gett_f32_kernels(&count);
-        g_launchCounts[2].fetch_add(1, std::memory_order_relaxed);
-        p.partial = (plan->choice.splitK > 1) ? static_cast<float*>(workspace) : nullptr;
-        {
-            static const int policy = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_PARTIAL_STORE"); return e ? (e[0] == 'p' ? 1 : e[0] == 'n' ? 2 : e[0] == 's' ? 3 : 0) : 0; }();   // hooks flavour; 's': the row epilogue skips its stores (timing only)
-            p.partialPolicy = policy;
-        }
-        if (plan->fusedFold) {
-            uint32_t slot;
-            {
-                std::lock_guard<std::mutex> g(handle->mtx);
-                slot = handle->syncNext++ % cutensorHandle::kSyncSlots;
-            }
-            p.sync = handle->syncPool + (size_t)slot * 16;
-        }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (handle->prof.enabled.load(std::memory_order_relaxed) && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
-            (void)hipEventRecord(e0, stream);
-        err = tab[plan->choice.kernel].launch(p, stream);
-        if (e0 && e1) {
-            (void)hipEventRecord(e1, stream);
-            std::lock_guard<std::mutex> g(handle->prof.mtx);
-            handle->prof.events.emplace_back(e0, e1);
-        }
-        if (err == hipSuccess && plan->choice.splitK > 1 && !plan->fusedFold && !handle->skipFold.load(std::memory_order_relaxed)) {
-            SplitKReduceParams r = plan->skr;
-            r.partial = static_cast<float*>(workspace);
-            r.C = p.C; r.D = D; r.alpha = p.alpha; r.beta = p.beta;
-            err = tab[plan->choice.kernel].fragPartials ? launch_splitk_reduce_frag(r, stream) : launch_splitk_reduce(r, stream);
-        }
     }
     if (t0 != nullptr) {
         if (err == hipSuccess && hipEventRecord(t1, stream) == hipSuccess) {
@@ -2235,24 +2212,19 @@ cutensorStatus_t cutensorContractTrinary(const cutensorHandle_t handle, const cu
                                          const void* A, const void* B, const void* C, const void* beta, const void* D, void* E,
                                          void* workspace, uint64_t workspaceSize, cudaStream_t stream) try {
     if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
-    if (plan == nullptr || plan->kind != OpKind::ContractionTrinary || plan->sub1 == nullptr || plan->sub2 == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
+    if (plan == nullptr || plan->kind != OpKind::ContractionTrinary || !plan->sub1 || !plan->sub2) return CUTENSOR_STATUS_INVALID_VALUE;
     if (alpha == nullptr || beta == nullptr || A == nullptr || B == nullptr || C == nullptr || E == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
     if (workspace == nullptr || workspaceSize < plan->requiredWorkspace) return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;
     if (misaligned(workspace, 128)) return CUTENSOR_STATUS_INVALID_VALUE;   // the intermediate and the sub-plans ask for 128 (contraction.cu:242 asserts no more)
     const void* in[3] = {A, B, C};
     const void *X = in[plan->triOrder[0]], *Y = in[plan->triOrder[1]], *Z = in[plan->triOrder[2]];
-    const uint64_t tOff = (plan->tBytes + 255) & ~255ull;
+    const uint64_t tOff = align256(plan->tBytes);
     void* T = workspace;
     void* ws = static_cast<char*>(workspace) + tOff;
-    // one / zero in the plan's scalar type; {re, im} pairs so that a complex scalar type reads a well-defined imaginary part
-    const double one64[2] = {1.0, 0.0}, zero64[2] = {0.0, 0.0};
-    const float one32[2] = {1.f, 0.f}, zero32[2] = {0.f, 0.f};
-    const bool f64 = plan->scalarType == HIP_R_64F || plan->scalarType == HIP_C_64F;
-    const void* one = f64 ? static_cast<const void*>(one64) : static_cast<const void*>(one32);
-    const void* zero = f64 ? static_cast<const void*>(zero64) : static_cast<const void*>(zero32);
-    cutensorStatus_t st = cutensorContract(handle, plan->sub1, one, X, Y, zero, T, T, ws, workspaceSize - tOff, stream);
+    const void *one = scalar_constant(plan->scalarType, true), *zero = scalar_constant(plan->scalarType, false);
+    cutensorStatus_t st = cutensorContract(handle, plan->sub1.get(), one, X, Y, zero, T, T, ws, workspaceSize - tOff, stream);
     if (st != CUTENSOR_STATUS_SUCCESS) return st;
-    return cutensorContract(handle, plan->sub2, alpha, T, Z, beta, D, E, ws, workspaceSize - tOff, stream);
+    return cutensorContract(handle, plan->sub2.get(), alpha, T, Z, beta, D, E, ws, workspaceSize - tOff, stream);
 } CTAMD_API_CATCH
 
 // contraction_jit.cu:134,398 — the engine has no run-time code generation (every kernel is compiled ahead of
@@ -2308,7 +2280,7 @@ size_t cutensorGetVersion(void) { return CUTENSOR_VERSION; }
 // them; returns how many there are, 0 for every other plan.  cuTENSORMg uses it to peel one digit of an oversized group into a
 // host loop (mg.cpp) instead of running the functional kernel.
 int ctamdPlanModeTableGroups(const cutensorPlan_t plan, int32_t* group, int32_t* label, int64_t* extent, int maxOut) try {
-    if (plan == nullptr || plan->kind != OpKind::Contraction || plan->choice.kernel != -2) return 0;
+    if (plan == nullptr || plan->kind != OpKind::Contraction || plan->planKind != PlanKind::ModeTable) return 0;
     if (plan->view.dtype == HIP_C_32F || plan->view.dtype == HIP_C_64F) return 0;     // complex data: not a matter of mode counts
     int n = 0;
     const std::vector<CanonMode>* gs[4] = {&plan->view.L, &plan->view.M, &plan->view.N, &plan->view.K};
@@ -2325,7 +2297,7 @@ int ctamdPlanModeTableGroups(const cutensorPlan_t plan, int32_t* group, int32_t*
 
 // Launches of the inner plan a peeled contraction plan makes per call (peel_wide_contraction); 0 for every other plan.
 int ctamdPlanPeelLaunches(const cutensorPlan_t plan) try {
-    if (plan == nullptr || plan->kind != OpKind::Contraction || plan->choice.kernel != -3) return 0;
+    if (plan == nullptr || plan->kind != OpKind::Contraction || plan->planKind != PlanKind::Peeled) return 0;
     long long n = 1;
     for (const PeelMode& pm : plan->peel) n *= pm.extent;
     return (int)n;
@@ -2347,6 +2319,9 @@ void ctamdPlanMemoStats(const cutensorHandle_t handle, uint64_t* hits, uint64_t*
     if (misses) *misses = handle->memoMisses.load(std::memory_order_relaxed);
     if (entries) { std::lock_guard<std::mutex> g(handle->mtx); *entries = (uint32_t)handle->planMemo.size(); }
 } CTAMD_API_CATCH_VOID
+// buf holds n characters of a plan's own keys, `{"key":..,"key":..,` — the keys of its inner plan follow: the inner plan's description is
+// written over the trailing ',' and its '{' turned into that ','
+static int describe_inner(const cutensorPlan& plan, char* buf, size_t len, int n);
 // Writes a one-line JSON description of the plan's kernel choice into buf.
 int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     if (plan == nullptr || buf == nullptr || len == 0) return -1;
@@ -2355,48 +2330,41 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     if (plan->kind == OpKind::ContractionTrinary)
         return std::snprintf(buf, len, "{\"op\":\"contraction_trinary\",\"intermediate_bytes\":%llu,\"workspace\":%llu}",
                              (unsigned long long)plan->tBytes, (unsigned long long)plan->requiredWorkspace);
-    if (plan->kind == OpKind::Contraction && plan->choice.kernel == -3 && plan->sub1 != nullptr) {
+    if (plan->kind == OpKind::Contraction && plan->planKind == PlanKind::Peeled && plan->sub1) {
         // peeled contraction: the inner (tiled) plan's description with the peel in front (and how many peeled modes are contracted ones)
         long long launches = 1;
         int contracted = 0;
         for (const PeelMode& pm : plan->peel) { launches *= pm.extent; contracted += pm.contracted ? 1 : 0; }
         n = std::snprintf(buf, len, "{\"peeled_modes\":%zu,\"peeled_contracted\":%d,\"peel_launches\":%lld,", plan->peel.size(), contracted, launches);
-        if (n < 0 || (size_t)n >= len) return -1;
-        const int m = ctamdDescribePlan(plan->sub1, buf + n - 1, len - (size_t)n + 1);   // overwrite our '{' + keep theirs: splice below
-        if (m < 0) return -1;
-        // buf now holds  {"peeled_modes":..,"peel_launches":..   followed (from n - 1) by the inner object  {...}: turn its '{' into ','
-        buf[n - 1] = ',';
-        return n - 1 + m;
+        return describe_inner(*plan, buf, len, n);
     }
-    if (plan->kind == OpKind::Contraction && plan->choice.kernel == -4 && plan->sub1 != nullptr) {
-        // a mode that one input alone carries: which operands are reduced first, then the inner contraction's description
-        const bool repA = plan->loneA && plan->loneA->kind == OpKind::Permutation, repB = plan->loneB && plan->loneB->kind == OpKind::Permutation;
+    if (plan->kind == OpKind::Contraction && (plan->planKind == PlanKind::LoneReduce || plan->planKind == PlanKind::Repack) && plan->sub1) {
+        // a two-step plan: which operands are reduced over their lone modes / copied into packed temporaries first, then the inner contraction's description
+        const bool rep = plan->planKind == PlanKind::Repack, hasA = (bool)plan->loneA, hasB = (bool)plan->loneB;
         n = std::snprintf(buf, len, "{\"lone_reduce_A\":%d,\"lone_reduce_B\":%d,\"repack_A\":%d,\"repack_B\":%d,\"lone_bytes\":%llu,",
-                          (plan->loneA && !repA) ? 1 : 0, (plan->loneB && !repB) ? 1 : 0, repA ? 1 : 0, repB ? 1 : 0,
+                          (hasA && !rep) ? 1 : 0, (hasB && !rep) ? 1 : 0, (hasA && rep) ? 1 : 0, (hasB && rep) ? 1 : 0,
                           (unsigned long long)(plan->loneBytesA + plan->loneBytesB));
-        if (n < 0 || (size_t)n >= len) return -1;
-        const int m = ctamdDescribePlan(plan->sub1, buf + n - 1, len - (size_t)n + 1);
-        if (m < 0) return -1;
-        buf[n - 1] = ',';
-        return n - 1 + m;
+        return describe_inner(*plan, buf, len, n);
     }
     if (plan->kind == OpKind::Contraction) {
+        // "kernel": the table index of a tiled plan, else the code tools know the plan kinds by
+        static const int kindCode[] = {0, -1, -2, -3, -4, -4};   // PlanKind::Tiled (unused), Simple, ModeTable, Peeled, LoneReduce, Repack
         int count = 0;
-        const GettKernelInfo* tab = (plan->choice.family == 2) ? gett_gen_kernels(&count) : (plan->choice.family == 1) ? gett_h16_kernels(&count) : gett_f32_kernels(&count);
-        const int k = plan->choice.kernel;
+        const GettKernelInfo* tab = kernel_table(plan->choice.family, &count);
+        const int k = plan->planKind == PlanKind::Tiled ? plan->choice.kernel : -1;
         n = std::snprintf(buf, len,
                           "{\"op\":\"contraction\",\"family\":%d,\"L\":%llu,\"M\":%llu,\"N\":%llu,\"K\":%llu,\"swapped\":%d,\"layA\":%d,\"layB\":%d,"
                           "\"kernel\":%d,\"bm\":%d,\"bn\":%d,\"bk\":%d,\"wm\":%d,\"wn\":%d,\"wk\":%d,\"pf\":%d,\"abl\":%d,\"splitK\":%u,\"kPerSlice\":%u,"
                           "\"blocks\":%u,\"workspace\":%llu,\"model_us\":%.2f,\"fusedFold\":%d,\"xcdTiles\":\"%016llx\",\"kname\":\"%s\"",
                           plan->choice.family, (unsigned long long)plan->view.totL, (unsigned long long)plan->view.totM,
                           (unsigned long long)plan->view.totN, (unsigned long long)plan->view.totK, (int)plan->view.swapped,
-                          plan->view.layA, plan->view.layB, k, k >= 0 ? tab[k].bm : 16, k >= 0 ? tab[k].bn : 16,
+                          plan->view.layA, plan->view.layB, k >= 0 ? k : kindCode[(int)plan->planKind], k >= 0 ? tab[k].bm : 16, k >= 0 ? tab[k].bn : 16,
                           k >= 0 ? tab[k].bk : 16, k >= 0 ? tab[k].wm : 1, k >= 0 ? tab[k].wn : 1, k >= 0 ? tab[k].wk : 1,
                           k >= 0 ? tab[k].pf : 0, k >= 0 ? tab[k].ablation : 0,
                           plan->gett.splitK, plan->gett.kPerSlice, plan->gett.nBlocks,
                           (unsigned long long)plan->requiredWorkspace, plan->choice.estimateUs, (int)plan->fusedFold,
                           (unsigned long long)plan->gett.xcdTiles,
-                          k == -2 ? "gett_wide_kernel" : k < 0 ? "gett_simple_kernel" : plan->choice.family == 2 ? (gen_elem_is_f32x(tab[k].elem) ? "gett_gen_f32x_kernel" : "gett_gen_kernel") : plan->choice.family == 1 ? (tab[k].threads == 256 || tab[k].pf == 10 ? (tab[k].bk == 32 ? "gett_h16w4s_kernel" : tab[k].pf == 3 ? "gett_h16w4r_kernel" : tab[k].pf == 6 ? "gett_h16w4v_kernel" : tab[k].pf == 7 ? "gett_h16w4x_kernel" : tab[k].pf == 8 ? "gett_h16w4m_kernel" : tab[k].pf == 9 ? "gett_h16w4m4_kernel" : tab[k].pf == 10 ? "gett_h16w8m_kernel" : tab[k].pf == 11 ? "gett_h16w4q_kernel" : tab[k].pf == 12 ? "gett_h16w4p_kernel" : "gett_h16w4_kernel") : tab[k].pf == 4 ? "gett_h16s_kernel" : "gett_h16_kernel") : tab[k].fragPartials ? "gett_f32_stream_kernel" : "gett_f32_kernel");
+                          k >= 0 ? tab[k].name : plan->planKind == PlanKind::ModeTable ? "gett_wide_kernel" : "gett_simple_kernel");
         // contracted digits, fastest first: [extent, strideA, strideB]
         if (n > 0 && (size_t)n < len && k >= 0)     // 1: the kernel streams its operands with the nontemporal policy (no Infinity-Cache allocation)
             n += std::snprintf(buf + n, len - n, ",\"nt\":%d", tab[k].nt);
@@ -2424,6 +2392,13 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     }
     return n;
 } CTAMD_API_CATCH_INT
+static int describe_inner(const cutensorPlan& plan, char* buf, size_t len, int n) {
+    if (n < 0 || (size_t)n >= len) return -1;
+    const int m = ctamdDescribePlan(plan.sub1.get(), buf + n - 1, len - (size_t)n + 1);
+    if (m < 0) return -1;
+    buf[n - 1] = ',';
+    return n - 1 + m;
+}
 
 // Diagnostics, all per handle.  Device buffer of 8 x uint64 per workgroup that the GETT kernel fills with phase
 // timestamps (shader clock and wall clock); nullptr switches it off.
@@ -2485,13 +2460,12 @@ int ctamdTestHooksBuilt(void) try { return CTAMD_HOOKS_BUILT; } CTAMD_API_CATCH_
 
 int ctamdKernelCount(void) try {
     int count = 0;
-    (void)gett_f32_kernels(&count);
+    (void)kernel_table(0, &count);
     return count;
 } CTAMD_API_CATCH_INT
 int ctamdKernelIsAblation(int i) try {
-    int count = 0;
-    const GettKernelInfo* tab = gett_f32_kernels(&count);
-    return (i >= 0 && i < count && tab[i].ablation) ? 1 : 0;
+    const GettKernelInfo* k = kernel_info(0, i);
+    return (k != nullptr && k->ablation) ? 1 : 0;
 } CTAMD_API_CATCH_INT
 
 // Number of ranked candidates for a contraction descriptor under a workspace limit (so that a

@@ -32,3 +32,6 @@
 #define CTAMD_HOOK_ENV(NAME) (static_cast<const char*>(nullptr))
 #define CTAMD_HOOKS_BUILT 0
 #endif
+// the switch is set and its value starts with CH (a macro, so that the production libraries do not hold the name either)
+#define CTAMD_HOOK_ENV_IS(NAME, CH) ctamd_starts_with(CTAMD_HOOK_ENV(NAME), CH)
+inline bool ctamd_starts_with(const char* value, char ch) { return value != nullptr && value[0] == ch; }

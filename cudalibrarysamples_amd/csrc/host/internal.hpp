@@ -41,7 +41,7 @@ struct cutensorTensorDescriptor {
     std::vector<int64_t> stride;
     hipDataType          dtype = HIP_R_32F;
     uint32_t             alignment = 0;
-    int64_t numElementsSpanned() const;  // 1 + sum (extent-1)*stride
+    int64_t numElementsSpanned() const { int64_t n = 1; for (uint32_t i = 0; i < numModes; ++i) n += (extent[i] - 1) * stride[i]; return n; }   // 1 + sum (extent-1)*stride
 };
 
 enum class OpKind : int { Contraction = 0, Reduction = 1, Permutation = 2, ElementwiseBinary = 3, ElementwiseTrinary = 4,
@@ -112,9 +112,19 @@ struct ContractionView {
     uint32_t alignD = 0;                 // ... of the output
 };
 
+// The shape of a contraction plan: what cutensorCreatePlan built and cutensorContract runs (cutensorPlan::planKind)
+enum class PlanKind : int {
+    Tiled,        // one launch of choice.kernel of choice.family (+ the split-K fold; + the strip launch of a strip plan)
+    Simple,       // gett_simple_kernel: no family has a kernel for the problem
+    ModeTable,    // gett_wide_kernel on cutensorPlan::wideTab
+    Peeled,       // a host loop over cutensorPlan::peel around sub1 (sub2: the accumulate launches)
+    LoneReduce,   // loneA / loneB reduce an operand over the modes it alone carries into a temporary, sub1 contracts the temporaries
+    Repack        // loneA / loneB copy an operand into a packed temporary, sub1 contracts the temporaries
+};
+
 // One executable choice for a contraction.
 struct ContractionChoice {
-    int      kernel = -1;      // index into the family's kernel table; -1 = simple kernel
+    int      kernel = -1;      // index into the family's kernel table; -1: none (PlanKind says what runs instead)
     int      family = 0;       // 0 = gett_f32_kernels() (fp32 data), 1 = gett_h16_kernels() (bf16 / fp16 data, aligned shapes),
                                // 2 = gett_gen_kernels() (general MFMA family: any 16-bit shape, fp64, complex; fp32 data under a reduced-precision compute descriptor)
     uint32_t splitK = 1;
@@ -141,6 +151,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
 // 16-bit family: the default kernel variant first, then the other variants of the same tile / split (the candidates
 // CUTENSOR_ALGO_DEFAULT_PATIENT and incremental autotuning measure)
 std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64_t wsLimit, int numCUs);
+int h16_waves_variant();   // the H16Variant CUTENSOR_AMD_H16_WAVES names (hooks flavour), else the default one
 void fill_gett_params(const ContractionView& v, const ContractionChoice& c, GettParams& p,
                       SplitKReduceParams& r);
 
@@ -201,21 +212,21 @@ struct PeelMode {
     bool    contracted = false;
 };
 
+// A plan is copyable (the plan memo clones prototypes): what it owns — sub-plans, finished and never changed after that, and the device
+// copy of its mode table — is shared with its copies and released with the last of them
+using SubPlan = std::shared_ptr<cutensorPlan>;
+
 struct cutensorPlan {
-    cutensorPlan() = default;
-    cutensorPlan(const cutensorPlan&) = default;   // valid only for plans that own nothing (sub1/sub2/wide.modes null): the memo's clones
-    ~cutensorPlan();
-    ctamd::WideParams wide{};        // mode-table contraction (view.wide): .modes is device memory owned by this plan,
-    std::vector<ctamd::WideMode> wideTab;   // uploaded from this host copy by the first cutensorContract
+    ctamd::WideParams wide{};        // mode-table contraction (PlanKind::ModeTable); .modes is filled per launch from wideDev,
+    std::vector<ctamd::WideMode> wideTab;   // uploaded from this host copy at plan creation or by the first cutensorContract
+    std::shared_ptr<const ctamd::WideMode> wideDev;
     // trinary contraction: the two pairwise plans, the intermediate's size and which operand plays which role
     std::shared_ptr<ctamd::BlockSparsePlan> bsp;     // block-sparse contraction: dense plans + block-pair task list
-    cutensorPlan* sub1 = nullptr;                    // (also: the inner plan of a peeled contraction, choice.kernel == -3)
-    cutensorPlan* sub2 = nullptr;
+    SubPlan sub1, sub2;                              // (also: the inner plans of a peeled contraction and sub1 of a two-step one)
     std::vector<PeelMode> peel;
-    // contraction with a mode that one input alone carries (choice.kernel == -4, api.cpp split_lone_modes): reductions of A / B over
-    // those modes into packed temporaries at the head of the workspace (nullptr: the operand is used as it is); sub1 = the contraction
-    cutensorPlan* loneA = nullptr;
-    cutensorPlan* loneB = nullptr;
+    // PlanKind::LoneReduce / Repack: the first step of A / B into packed temporaries at the head of the workspace (null: the operand is
+    // used as it is); sub1 = the contraction
+    SubPlan loneA, loneB;
     uint64_t    loneBytesA = 0, loneBytesB = 0;
     // fp16 reductions: the temporary holds sum * 2^-loneShift, loneShift = ceil(log2(n) / 2) for n summed elements, and the inner
     // contraction's alpha takes 2^(loneShiftA + loneShiftB) back (both factors exact).  Half the exponent of n, not all of it: a coherent
@@ -233,6 +244,7 @@ struct cutensorPlan {
     // contraction
     ctamd::ContractionView     view;
     ctamd::ContractionChoice   choice;
+    ctamd::PlanKind            planKind = ctamd::PlanKind::Simple;
     ctamd::GettParams          gett{};
     ctamd::SplitKReduceParams  skr{};
     bool                       accumulate64 = false;

@@ -331,7 +331,8 @@ static double tile_efficiency(const GettKernelInfo& k) {
     // 6-deep ones in the device's steady clock state (headline einsum 42.5 vs 43.6 us per step)
     // (compute-bound problems: the 4-deep ring — 4096^3 128 x 128: 148 TFLOP/s against 130 on the 3-deep one, 4098^3 alike,
     // profiles/r06i_f32_candidates_4098_4096.jsonl; memory-bound ones tie here and the 3-deep ring wins the tie-break below)
-    if (k.fragPartials) return area >= 96 * 96 ? (k.pf == 4 ? 0.93 : 0.92) : 0.75;
+    const int ringDepth = k.pf;   // (fp32 ring kernels)
+    if (k.fragPartials) return area >= 96 * 96 ? (ringDepth == 4 ? 0.93 : 0.92) : 0.75;
     if (area >= 128 * 128) return 0.85;
     if (area >= 96 * 96) return 0.80;
     if (area >= 64 * 64) return 0.65;
@@ -450,7 +451,8 @@ std::vector<ContractionChoice> rank_contraction_choices(const ContractionView& v
             const double tRound = (roundsEff > 1.0) ? (roundsEff - 1.0) * (2.0e-6 + 0.34e-6 * (double)(k.bm * k.bn) / 1024.0) * shortK : 0.0;
             const double tFix = ((c.splitK > 1) ? 3.0e-6 + tFold : 0.0) + tRound;
             c.estimateUs = (std::max(tCompute, tMem) + tFix + 2.0e-6) * 1e6;
-            if (k.fragPartials && k.pf == 3) c.estimateUs *= 0.999;   // tie-break for memory-bound estimates: the 3-deep ring wins by ~2 %
+            const int ringDepth = k.pf;
+            if (k.fragPartials && ringDepth == 3) c.estimateUs *= 0.999;   // tie-break for memory-bound estimates: the 3-deep ring wins by ~2 %
             if (k.nt) c.estimateUs *= 0.96;                            // eligible (see above): ahead of its default-policy twin
             out.push_back(c);
         }
@@ -500,6 +502,21 @@ static bool h16_needs_rag(const ContractionView& v) {
     return false;
 }
 
+// CUTENSOR_AMD_H16_WAVES (hooks flavour, read once) names a variant of the family by a prefix of its value, the first match counts;
+// unset or unknown: the default variant
+int h16_waves_variant() {
+    static const struct { const char* prefix; H16Variant variant; } names[] = {
+        {"4s", H16_W4S}, {"4r", H16_W4R}, {"4v", H16_W4V}, {"4x", H16_W4X}, {"4p", H16_W4P}, {"4q", H16_W4Q}, {"8m", H16_W8M},
+        {"4m4", H16_W4M4}, {"4m", H16_W4M}, {"4", H16_W4}, {"s", H16_S}, {"8", H16_W8}, {"p", H16_W8}};
+    static const int variant = [] {
+        const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES");
+        for (const auto& n : names)
+            if (e && std::strncmp(e, n.prefix, std::strlen(n.prefix)) == 0) return (int)n.variant;
+        return (int)H16_W4X;
+    }();
+    return variant;
+}
+
 bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c) {
     if (v.dtype != HIP_R_16BF && v.dtype != HIP_R_16F) return false;
     if ((v.layA != LAY_K && v.layA != LAY_F) || (v.layB != LAY_K && v.layB != LAY_F)) return false;
@@ -535,36 +552,19 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     c = ContractionChoice{};
     c.family = 1;
     c.kernel = (v.dtype == HIP_R_16BF ? 0 : 4) + (v.layA == LAY_F ? 2 : 0) + (v.layB == LAY_F ? 1 : 0);
-    // entries 0..7: eight waves, two rows alternated by barriers (ping-pong); 8..15: four waves per workgroup (one per
-    // SIMD); 16..23: eight free-running waves, K-tile of 32, deep LDS ring, one barrier per K-tile; 24..31: four waves on that
-    // ring; 32..39: four waves, register-staged; 40..47: four waves, lean instruction stream (gett_h16v.hip); 48..55: the same on
-    // the 16x16x32 MFMA — the default since round 3 (+8-14 % under the power limit on every layout)
-    static const int variant = [] {
-        const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES");
-        if (e && e[0] == '4' && e[1] == 's') return 24;
-        if (e && e[0] == '4' && e[1] == 'r') return 32;
-        if (e && e[0] == '4' && e[1] == 'v') return 40;
-        if (e && e[0] == '4' && e[1] == 'x') return 48;
-        if (e && e[0] == '4' && e[1] == 'p') return 88;
-        if (e && e[0] == '4' && e[1] == 'q') return 80;
-        if (e && e[0] == '8' && e[1] == 'm') return 72;
-        if (e && e[0] == '4' && e[1] == 'm' && e[2] == '4') return 64;
-        if (e && e[0] == '4' && e[1] == 'm') return 56;
-        if (e && e[0] == '4') return 8;
-        if (e && e[0] == 's') return 16;
-        if (e && (e[0] == '8' || e[0] == 'p')) return 0;
-        return 48;
-    }();
+    // the variants are listed with H16Variant (kernels/launch.h); H16_W4X is the default since round 3 (+8-14 % under the power limit
+    // on every layout)
+    const int variant = h16_waves_variant();
+    const bool forced = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") != nullptr;
     const int layoutIdx = c.kernel;
     const uint64_t kTiles = h16_k_tiles(v);
     const uint64_t perSliceBytes = v.totL * v.totM * v.totN * 4ull;
-    const bool forced = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") != nullptr;
     auto tiles_of = [&](int var) {
         const GettKernelInfo& k = tab[layoutIdx + var];
         return std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
     };
-    // workgroup slots of the chip: the 128 x 128 kernel on the two-deep ring (variant 56) runs two workgroups per CU
-    auto slots_of = [&](int var) { return (double)numCUs * ((var == 56 || var == 80) ? 2.0 : 1.0); };
+    // workgroup slots of the chip: the 128 x 128 kernel on the two-deep ring (H16_W4M) runs two workgroups per CU
+    auto slots_of = [&](int var) { return (double)numCUs * ((var == H16_W4M || var == H16_W4Q) ? 2.0 : 1.0); };
     // split-K when the output tiles alone leave most CUs idle: slices of >= 4 K-tiles, fp32 partials [slice][L][M][N]
     auto auto_split = [&](int var) -> uint64_t {
         const double tiles = tiles_of(var), slots = slots_of(var);
@@ -578,37 +578,37 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     };
     // Time model (us) of a variant at a split, from the shape sweeps of round 4 (profiles/r04*_h16_shape_sweep*: 8192^3 .. 256^2 x 16384 on
     // all variants): rounds x (fixed cost per workgroup + K-tiles x time per K-tile) + the fold.  Only has to ORDER the candidates.
-    //   256 x 256, four waves (48):  10 us fixed, 1.00 us per K-tile      (256 x 256, eight waves (0): 10 us fixed, 1.13 us per K-tile)
-    //   128 x 128, ring 2 (56), two workgroups per CU: 5 us fixed, 0.92 us per K-tile (0.68 with the CU to itself)
-    //   128 x 128, ring 4 (64), one workgroup per CU:  4.5 us fixed, 0.46 us per K-tile
-    //   64 x 64 (80), two workgroups per CU: 4.6 us fixed, 0.31 us per K-tile (4.4 / 0.223 while every workgroup has a CU to itself;
+    //   256 x 256, four waves (H16_W4X):  10 us fixed, 1.00 us per K-tile      (256 x 256, eight waves (H16_W8): 10 us fixed, 1.13 us per K-tile)
+    //   128 x 128, ring 2 (H16_W4M), two workgroups per CU: 5 us fixed, 0.92 us per K-tile (0.68 with the CU to itself)
+    //   128 x 128, ring 4 (H16_W4M4), one workgroup per CU:  4.5 us fixed, 0.46 us per K-tile
+    //   64 x 64 (H16_W4Q), two workgroups per CU: 4.6 us fixed, 0.31 us per K-tile (4.4 / 0.223 while every workgroup has a CU to itself;
     //   profiles/r04w_sweep_4q_*: 1024^3 7.6-7.9 us, 4096^3 195-202 us)
     //   fold (splitk_reduce_wide_kernel): 3 us + partial bytes written and read back at ~5 TB/s
     auto model_tiles_us = [&](int var, double tiles, uint64_t split) {
         const double wgs = tiles * (double)split, slots = slots_of(var);
         const double kt = std::ceil((double)kTiles / (double)split);
         double fix, per;
-        if (var == 64) { fix = 4.5; per = 0.46; }
-        else if (var == 80) { fix = wgs <= (double)numCUs ? 4.4 : 4.6; per = wgs <= (double)numCUs ? 0.223 : 0.31; }
-        else if (var == 56) { fix = 5.0; per = wgs <= (double)numCUs ? 0.68 : 0.92; }
+        if (var == H16_W4M4) { fix = 4.5; per = 0.46; }
+        else if (var == H16_W4Q) { fix = wgs <= (double)numCUs ? 4.4 : 4.6; per = wgs <= (double)numCUs ? 0.223 : 0.31; }
+        else if (var == H16_W4M) { fix = 5.0; per = wgs <= (double)numCUs ? 0.68 : 0.92; }
         else { fix = 10.0; per = 1.0; }
         double t = std::ceil(wgs / slots) * (fix + kt * per);
-        // the persistent form of the 256 x 256 kernel (88, gett_h16p.hip, round 5): a workgroup walks its tiles, interior tiles with an even
+        // the persistent form of the 256 x 256 kernel (H16_W4P, gett_h16p.hip, round 5): a workgroup walks its tiles, interior tiles with an even
         // K-tile count stream into each other (the next tile's first K-tiles are fetched by the last K-tile bodies) — the first tile costs
         // what gett_h16w4x_kernel's does plus ~0.5 us of extra setup, every further one ~6 us less (profiles/r05e_h16p_vs_4x.jsonl: 8192^2 x
         // 512 / 1024 / 2048 / 4096 / 8192 +6.8 / +3.3 / +2.5 / +1.8 / +0.8 %, one-round shapes -1 %)
-        if (var == 88) { const double ke = kt + (std::fmod(kt, 2.0) != 0.0 ? 1.0 : 0.0); t = 10.5 + ke * per + (std::ceil(wgs / slots) - 1.0) * (4.5 + ke * per); }
+        if (var == H16_W4P) { const double ke = kt + (std::fmod(kt, 2.0) != 0.0 ? 1.0 : 0.0); t = 10.5 + ke * per + (std::ceil(wgs / slots) - 1.0) * (4.5 + ke * per); }
         if (split > 1) t += 3.0 + 2.0 * (double)split * (double)perSliceBytes / 5.0e6;
         return t;
     };
     auto model_us = [&](int var, uint64_t split) { return model_tiles_us(var, tiles_of(var), split); };
     // Strip plan of a candidate (round 6): its whole tiles as the interior launch, the two edge strips as ONE launch of the 64 x 64 kernel
-    // (entry 80: two tile rectangles in one grid, GettParams::tilesM2).  Worth it when the partial tiles push the launch into another
+    // (H16_W4Q: two tile rectangles in one grid, GettParams::tilesM2).  Worth it when the partial tiles push the launch into another
     // round: 4100^3 on 256 x 256 tiles = 289 tiles = two rounds (150 us by this model) against 256 tiles + 129 strip tiles (~97 us).
     // One M and one N mode only (a strip is a contiguous index range of a mode group, but the interior's whole-tile test and the
     // kernels' edge clamps are written for it), no split-K.  Returns the model time, 1e30 when the candidate has no strip form.
     auto strip_us = [&](int cand, uint32_t& mInt, uint32_t& nInt) {
-        if (layoutIdx + 80 >= count || layoutIdx + cand >= count) return 1e30;
+        if (layoutIdx + H16_W4Q >= count || layoutIdx + cand >= count) return 1e30;
         const GettKernelInfo& k = tab[layoutIdx + cand];
         if (k.bm <= 64) return 1e30;
         mInt = (uint32_t)(v.totM / k.bm) * (uint32_t)k.bm;
@@ -617,39 +617,40 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         const double tilesInt = (double)(mInt / k.bm) * (double)(nInt / k.bn) * (double)v.totL;
         const double strip = (std::ceil((double)(v.totM - mInt) / 64.0) * std::ceil((double)v.totN / 64.0) +
                               std::ceil((double)mInt / 64.0) * std::ceil((double)(v.totN - nInt) / 64.0)) * (double)v.totL;
-        return model_tiles_us(cand, tilesInt, 1) + model_tiles_us(80, strip, 1) + 1.5;   // + the gap between the two launches
+        return model_tiles_us(cand, tilesInt, 1) + model_tiles_us(H16_W4Q, strip, 1) + 1.5;   // + the gap between the two launches
     };
     static const bool noStrips = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_STRIPS"); return e && e[0] == '0'; }();
     const bool stripsOK = !noStrips && v.M.size() == 1 && v.N.size() == 1;
     int var = variant;
     uint64_t split = 1;
+    // the best of the candidates considered so far by the model: each without split-K, at its automatic split and as a strip plan
+    double best = 1e30;
+    auto consider = [&](int cand) {
+        if (layoutIdx + cand >= count) return;
+        const uint64_t as = auto_split(cand);
+        for (uint64_t sp : {(uint64_t)1, as}) {
+            const double t = model_us(cand, sp);
+            if (t < best) { best = t; var = cand; split = sp; c.stripKernel = -1; }
+            if (as == 1) break;
+        }
+        uint32_t mi = 0, ni = 0;
+        const double ts = stripsOK ? strip_us(cand, mi, ni) : 1e30;
+        if (ts < 0.97 * best) { best = ts; var = cand; split = 1; c.stripKernel = h16_entry(H16_W4Q, layoutIdx); c.mInt = mi; c.nInt = ni; }
+    };
     const bool usable = forced && layoutIdx + var < count && tab[layoutIdx + var].ablation != 2;   // a retired family asked for in a production build: ignored
     if (ragged && forced) {
         // CUTENSOR_AMD_H16_WAVES names the kernel: one of those that mask a partial K-tile (4x, 4m, 4m4, 4q), or the general family
-        if (!usable || (var != 48 && var != 56 && var != 64 && var != 80)) return false;
+        if (!usable || (var != H16_W4X && var != H16_W4M && var != H16_W4M4 && var != H16_W4Q)) return false;
         split = auto_split(var);
     } else if (ragged) {
         // the kernels of the family that mask a partial K-tile (the RAG instantiations): the 256 x 256 four-wave kernel, the 128 x 128
         // pair and the 64 x 64 tile — every candidate of the planner but the persistent kernel
-        double best = 1e30;
-        for (int cand : {48, 64, 56, 80}) {
-            if (layoutIdx + cand >= count) continue;
-            const uint64_t as = auto_split(cand);
-            for (uint64_t sp : {(uint64_t)1, as}) {
-                const double t = model_us(cand, sp);
-                if (t < best) { best = t; var = cand; split = sp; c.stripKernel = -1; }
-                if (as == 1) break;
-            }
-            uint32_t mi = 0, ni = 0;
-            const double ts = stripsOK ? strip_us(cand, mi, ni) : 1e30;
-            if (ts < 0.97 * best) { best = ts; var = cand; split = 1; c.stripKernel = layoutIdx + 80; c.mInt = mi; c.nInt = ni; }
-        }
+        for (int cand : {H16_W4X, H16_W4M4, H16_W4M, H16_W4Q}) consider(cand);
     } else if (forced && usable) {
         split = auto_split(var);
     } else {
         // the planner's own choice: the 256 x 256 family (four-wave 16x16x32 kernel; eight-wave kernel for short K ranges, below), the
         // 128 x 128 mid-size family and the 64 x 64 tile, each without split-K and at its automatic split
-        double best = 1e30;
         static const bool noPersistent = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16P"); return e && e[0] == '0'; }();
         // The persistent kernel earns its place by streaming interior tiles into each other, which needs the epilogue that stays out of the
         // operand ring (gett_h16p.hip, curOK): one M and one N mode, 16-byte lanes in D (batch modes stream since round 6).  Tiles that cannot stream are set up
@@ -662,19 +663,8 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         // the 7.8k-cycle prologue it saves per tile: up to 15 K-tiles (K = 64: attention scores with 64-wide heads)
         const bool streamable = v.M.size() == 1 && v.N.size() == 1 && v.N[0].sD == 1 && v.N[0].extent % 8 == 0 &&
                                 v.M[0].sD % 8 == 0 && v.alignD % 16 == 0 && (kTiles % 2 == 0 || kTiles <= 15);
-        for (int cand : {48, 88, 64, 56, 80}) {
-            if (cand == 88 && (noPersistent || !streamable)) continue;
-            if (layoutIdx + cand >= count) continue;
-            const uint64_t as = auto_split(cand);
-            for (uint64_t sp : {(uint64_t)1, as}) {
-                const double t = model_us(cand, sp);
-                if (t < best) { best = t; var = cand; split = sp; c.stripKernel = -1; }
-                if (as == 1) break;
-            }
-            uint32_t mi = 0, ni = 0;
-            const double ts = stripsOK ? strip_us(cand, mi, ni) : 1e30;
-            if (ts < 0.97 * best) { best = ts; var = cand; split = 1; c.stripKernel = layoutIdx + 80; c.mInt = mi; c.nInt = ni; }
-        }
+        for (int cand : {H16_W4X, H16_W4P, H16_W4M4, H16_W4M, H16_W4Q})
+            if (cand != H16_W4P || (!noPersistent && streamable)) consider(cand);
     }
     c.kernel = layoutIdx + var;
     if (const char* fs = ctamd_research_env("CUTENSOR_AMD_H16_SPLITK")) {   // measurement knob: this many slices (if the workspace allows)
@@ -701,9 +691,9 @@ std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64
     out.push_back(base);
     if (h16_needs_rag(v)) return out;              // ragged K / partial units: the planner's pick among the kernels that mask (pick_h16_choice)
     int count = 0;
-    const int layoutIdx = base.kernel % 8, variant = base.kernel - layoutIdx;
     const GettKernelInfo* tab = gett_h16_kernels(&count);
-    for (int other : {0, 48, 88, 56, 64, 72, 80, 40, 32, 16, 24, 8}) {  // ping-pong rows, four waves register-staged, streamed (free-running waves), four waves streamed, four waves
+    const int variant = tab[base.kernel].variant, layoutIdx = base.kernel - variant;
+    for (int other : {H16_W8, H16_W4X, H16_W4P, H16_W4M, H16_W4M4, H16_W8M, H16_W4Q, H16_W4V, H16_W4R, H16_S, H16_W4S, H16_W4}) {
         if (other == variant || layoutIdx + other >= count) continue;
         if (tab[layoutIdx + other].ablation == 2) continue;        // a retired family, not built into this library (research builds only)
         ContractionChoice c = base;

@@ -277,7 +277,7 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     }
     // EW_TRANSPOSE_ANY (round 6): what is left for the element-gather kernel although it IS a transposition — D contiguous along dim0, A
     // along dim1, but odd extents / strides / base alignment (4097 x 4099: 0.9-1.5 TB/s there, each lane of a load on another line)
-    const bool anyForced = CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") && CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY")[0] == '1';   // measurement: also where the 16-byte-lane kernel applies
+    const bool anyForced = CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_EW_ANY", '1');   // measurement: also where the 16-byte-lane kernel applies
     // ... and it is the faster kernel for MID-SIZE pure permutations the 16-byte-lane kernels do take: their wide tiles (fp32: 256 x 64)
     // leave a 4096^2 transposition on 1024 workgroups — 4.6 TB/s against 5.9 on 4096 tiles of 64 x 64 — and rows whose pitch is no
     // multiple of 128 bytes cost them more (4104^2: 3.4 / 5.2; bf16 on the narrow 64 x 64 kernel 2.6 / 3.4).  Large tensors stay
@@ -287,7 +287,7 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     // fp32 below 512 MB, the narrow 16-bit kernel below 1 GB.
     const uint64_t vecTiles = (uint64_t)((p.E0 + t0 - 1) / t0) * (uint64_t)((p.E1 + t1 - 1) / t1) * (uint64_t)p.rest.total;
     const uint64_t tensorBytes = (uint64_t)p.E0 * (uint64_t)p.E1 * (uint64_t)p.rest.total * (uint64_t)dtype_size(D.desc.dtype);
-    const bool anyOff = CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") && CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY")[0] == '0';      // tests: the 16-byte-lane kernels on small tensors
+    const bool anyOff = CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_EW_ANY", '0');      // tests: the 16-byte-lane kernels on small tensors
     const bool midSize = !anyOff && plan.variant == EW_TRANSPOSE && ((D.desc.dtype == HIP_R_32F && (vecTiles < 4096 || tensorBytes < (512ull << 20))) ||
                                                                      (h16 && t0 == 64 && (vecTiles < 16384 || tensorBytes < (1ull << 30))));
     // (the binary form of cutensorElementwiseBinaryExecute too — allowWide tells it from the trinary planner's passes, which attach E / X

@@ -911,10 +911,10 @@ static hipError_t launch_pingpong(const GettParams& p, hipStream_t stream) {
 
 #define CTAMD_ENTRY(bm, bn, bk, wm, wn, wk, la, lb, minw, pf, kfast) \
     {bm, bn, bk, wm, wn, wk, la, lb, 64 * wm * wn * wk, pf, kfast ? 1 : 0, 0, \
-     &launch_cfg<GettCfg<bm, bn, bk, wm, wn, wk, la, lb, minw, pf, kfast>>},
+     &launch_cfg<GettCfg<bm, bn, bk, wm, wn, wk, la, lb, minw, pf, kfast>>, 0, 0, 0, 0, "gett_f32_kernel"},
 #define CTAMD_ENTRY3(bm, bn, bk, wm, wn, wk, la, lb, minw, pf) \
     {bm, bn, bk, wm, wn, wk, la, lb, 64 * wm * wn * wk, pf, 1, 0, \
-     &launch_cfg<GettCfg<bm, bn, bk, wm, wn, wk, la, lb, minw, pf, true, 0, 3>>},
+     &launch_cfg<GettCfg<bm, bn, bk, wm, wn, wk, la, lb, minw, pf, true, 0, 3>>, 0, 0, 0, 0, "gett_f32_kernel"},
 // two-team ping-pong kernels: XP(bm, bn, bk, wm, wn, layA, layB, pf, kfast)
 #define CTAMD_PINGPONG_KERNELS(XP)             \
     XP(96, 96, 32, 2, 2, LAY_K, LAY_F, 2, true)  \
@@ -925,11 +925,11 @@ static hipError_t launch_pingpong(const GettParams& p, hipStream_t stream) {
     XP(64, 64, 32, 2, 2, LAY_K, LAY_F, 2, false)
 #define CTAMD_ENTRYP(bm, bn, bk, wm, wn, la, lb, pf, kfast) \
     {bm, bn, bk, wm, wn, 1, la, lb, 2 * 64 * wm * wn, pf, kfast ? 1 : 0, 0, \
-     &launch_pingpong<GettCfg<bm, bn, bk, wm, wn, 1, la, lb, 2, pf, kfast>>},
+     &launch_pingpong<GettCfg<bm, bn, bk, wm, wn, 1, la, lb, 2, pf, kfast>>, 0, 0, 0, 0, "gett_f32_kernel"},
 // measurement-only ablations of the headline kernel (never ranked unless CUTENSOR_AMD_ABLATION is set)
 #define CTAMD_ABL_ENTRY(bm, bn, bk, wm, wn, wk, la, lb, minw, pf, abl) \
     {bm, bn, bk, wm, wn, wk, la, lb, 64 * wm * wn * wk, pf, 1, abl, \
-     &launch_cfg<GettCfg<bm, bn, bk, wm, wn, wk, la, lb, minw, pf, true, abl>>},
+     &launch_cfg<GettCfg<bm, bn, bk, wm, wn, wk, la, lb, minw, pf, true, abl>>, 0, 0, 0, 0, "gett_f32_kernel"},
 
 static const GettKernelInfo g_gett_f32_table[] = {
     CTAMD_ALL_KERNELS(CTAMD_ENTRY)

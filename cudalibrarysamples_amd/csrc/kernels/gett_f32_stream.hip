@@ -959,13 +959,13 @@ static hipError_t launch_stream(const GettParams& p, hipStream_t stream) {
     XS(128, 128, LAY_K, LAY_F, 3)
 
 #define CTAMD_STREAM_ENTRY(bm, bn, la, lb, s) \
-    {bm, bn, kStreamBK, 2, 2, 1, la, lb, 512, s, 1, 0, &launch_stream<StreamCfg<bm, bn, la, lb, s>>, 1},
+    {bm, bn, kStreamBK, 2, 2, 1, la, lb, 512, s, 1, 0, &launch_stream<StreamCfg<bm, bn, la, lb, s>>, 1, 0, 0, 0, "gett_f32_stream_kernel"},
 
 #define CTAMD_STREAM_ABL(bm, bn, la, lb, s, abl) \
-    {bm, bn, kStreamBK, 2, 2, 1, la, lb, 512, s, 1, abl, &launch_stream<StreamCfg<bm, bn, la, lb, s, abl>>, 1},
+    {bm, bn, kStreamBK, 2, 2, 1, la, lb, 512, s, 1, abl, &launch_stream<StreamCfg<bm, bn, la, lb, s, abl>>, 1, 0, 0, 0, "gett_f32_stream_kernel"},
 
 #define CTAMD_STREAM_NT(bm, bn, la, lb, s) \
-    {bm, bn, kStreamBK, 2, 2, 1, la, lb, 512, s, 1, 0, &launch_stream<StreamCfg<bm, bn, la, lb, s, 5>>, 1, 1},
+    {bm, bn, kStreamBK, 2, 2, 1, la, lb, 512, s, 1, 0, &launch_stream<StreamCfg<bm, bn, la, lb, s, 5>>, 1, 1, 0, 0, "gett_f32_stream_kernel"},
 
 static const GettKernelInfo g_stream_table[] = {
     CTAMD_STREAM_KERNELS(CTAMD_STREAM_ENTRY)

@@ -463,7 +463,7 @@ static hipError_t launch_gen(const GettParams& p, hipStream_t stream) {
 
 // table entry: {bm, bn, bk, wm, wn, wk, layA, layB, threads, pf, kfast, ablation, launch, fragPartials, nt, elem, vec}
 #define CTAMD_GEN_ENTRY(GE, BM, BN, BK, OA, OB, V) \
-    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen<GenCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V},
+    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen<GenCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V, "gett_gen_kernel"},
 // the four orientation pairs (LAY_F = 0: free-contiguous, LAY_K = 1: K-contiguous) of one (type, tile, vector width)
 #define CTAMD_GEN_ORIENTS(GE, BM, BN, BK, V)   \
     CTAMD_GEN_ENTRY(GE, BM, BN, BK, 0, 0, V)   \

@@ -321,7 +321,7 @@ static hipError_t launch_gen_f32x(const GettParams& p, hipStream_t stream) {
 
 // table entry: {bm, bn, bk, wm, wn, wk, layA, layB, threads, pf, kfast, ablation, launch, fragPartials, nt, elem, vec}
 #define CTAMD_F32X_ENTRY(GE, BM, BN, BK, OA, OB, V) \
-    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen_f32x<F32xCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V},
+    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen_f32x<F32xCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V, "gett_gen_f32x_kernel"},
 // the four orientation pairs (LAY_F = 0: free-contiguous, LAY_K = 1: K-contiguous) of one (mode, tile, vector width)
 #define CTAMD_F32X_ORIENTS(GE, BM, BN, BK, V)   \
     CTAMD_F32X_ENTRY(GE, BM, BN, BK, 0, 0, V)   \

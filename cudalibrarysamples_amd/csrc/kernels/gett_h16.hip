@@ -1376,52 +1376,52 @@ namespace ctamd {
 // bf16 entries first, then fp16, each in the order (layA, layB) = (K,K) (K,F) (F,K) (F,F)
 #if !defined(CTAMD_RESEARCH_KERNELS)
 static hipError_t launch_h16_not_built(const GettParams&, hipStream_t) { return hipErrorNotSupported; }
-#define CTAMD_H16_ENTRY(bf, la, lb)    {kHTile, kHTile, kHBK, 2, 4, 1, la, lb, 512, 5, 1, 2, &launch_h16_not_built, 0},
-#define CTAMD_H16W4_ENTRY(bf, la, lb)  {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 2, 1, 2, &launch_h16_not_built, 0},
-#define CTAMD_H16S_ENTRY(bf, la, lb)   {kHTile, kHTile, 32, 2, 4, 1, la, lb, 512, 4, 1, 2, &launch_h16_not_built, 0},
-#define CTAMD_H16W4R_ENTRY(bf, la, lb) {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 3, 1, 2, &launch_h16_not_built, 0},
-#define CTAMD_H16W4S_ENTRY(bf, la, lb) {kHTile, kHTile, 32, 2, 2, 1, la, lb, 256, 5, 1, 2, &launch_h16_not_built, 0},
+#define CTAMD_H16_ENTRY(bf, la, lb)    {kHTile, kHTile, kHBK, 2, 4, 1, la, lb, 512, 5, 1, 2, &launch_h16_not_built, 0, 0, 0, 0, "gett_h16_kernel", H16_W8},
+#define CTAMD_H16W4_ENTRY(bf, la, lb)  {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 2, 1, 2, &launch_h16_not_built, 0, 0, 0, 0, "gett_h16w4_kernel", H16_W4},
+#define CTAMD_H16S_ENTRY(bf, la, lb)   {kHTile, kHTile, 32, 2, 4, 1, la, lb, 512, 4, 1, 2, &launch_h16_not_built, 0, 0, 0, 0, "gett_h16s_kernel", H16_S},
+#define CTAMD_H16W4R_ENTRY(bf, la, lb) {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 3, 1, 2, &launch_h16_not_built, 0, 0, 0, 0, "gett_h16w4r_kernel", H16_W4R},
+#define CTAMD_H16W4S_ENTRY(bf, la, lb) {kHTile, kHTile, 32, 2, 2, 1, la, lb, 256, 5, 1, 2, &launch_h16_not_built, 0, 0, 0, 0, "gett_h16w4s_kernel", H16_W4S},
 #else
 #define CTAMD_H16_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 4, 1, la, lb, 512, 5, 1, 0, &launch_h16<bf, la, lb>, 0},
+    {kHTile, kHTile, kHBK, 2, 4, 1, la, lb, 512, 5, 1, 0, &launch_h16<bf, la, lb>, 0, 0, 0, 0, "gett_h16_kernel", H16_W8},
 #define CTAMD_H16W4_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 2, 1, 0, &launch_h16w4<bf, la, lb>, 0},
+    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 2, 1, 0, &launch_h16w4<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4_kernel", H16_W4},
 #define CTAMD_H16S_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kSBK, 2, 4, 1, la, lb, 512, 4, 1, 0, &launch_h16s<bf, la, lb>, 0},
+    {kHTile, kHTile, kSBK, 2, 4, 1, la, lb, 512, 4, 1, 0, &launch_h16s<bf, la, lb>, 0, 0, 0, 0, "gett_h16s_kernel", H16_S},
 #define CTAMD_H16W4R_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 3, 1, 0, &launch_h16w4r<bf, la, lb>, 0},
+    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 3, 1, 0, &launch_h16w4r<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4r_kernel", H16_W4R},
 #define CTAMD_H16W4S_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kSBK, 2, 2, 1, la, lb, 256, 5, 1, 0, &launch_h16w4s<bf, la, lb>, 0},
+    {kHTile, kHTile, kSBK, 2, 2, 1, la, lb, 256, 5, 1, 0, &launch_h16w4s<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4s_kernel", H16_W4S},
 #endif
 static const GettKernelInfo g_h16_table[] = {
     CTAMD_H16_ENTRY(true, LAY_K, LAY_K) CTAMD_H16_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16_ENTRY(true, LAY_F, LAY_K) CTAMD_H16_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16_ENTRY(false, LAY_K, LAY_K) CTAMD_H16_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16_ENTRY(false, LAY_F, LAY_K) CTAMD_H16_ENTRY(false, LAY_F, LAY_F)
-    // entries 8..15: the four-wave variant, same order
+    // H16_W4: the four-wave variant, same order
     CTAMD_H16W4_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4_ENTRY(false, LAY_F, LAY_F)
-    // entries 16..23: the streamed eight-wave variant (free-running waves, K-tile 32, deep LDS ring), same order
+    // H16_S: the streamed eight-wave variant (free-running waves, K-tile 32, deep LDS ring), same order
     CTAMD_H16S_ENTRY(true, LAY_K, LAY_K) CTAMD_H16S_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16S_ENTRY(true, LAY_F, LAY_K) CTAMD_H16S_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16S_ENTRY(false, LAY_K, LAY_K) CTAMD_H16S_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16S_ENTRY(false, LAY_F, LAY_K) CTAMD_H16S_ENTRY(false, LAY_F, LAY_F)
-    // entries 24..31: the four-wave streamed variant (128 x 128 wave tiles on the K-tile-32 ring), same order
+    // H16_W4S: the four-wave streamed variant (128 x 128 wave tiles on the K-tile-32 ring), same order
     CTAMD_H16W4S_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4S_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4S_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4S_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4S_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4S_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4S_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4S_ENTRY(false, LAY_F, LAY_F)
-    // entries 32..39: the four-wave register-staged variant (no LDS-DMA), same order
+    // H16_W4R: the four-wave register-staged variant (no LDS-DMA), same order
     CTAMD_H16W4R_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4R_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4R_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4R_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4R_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4R_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4R_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4R_ENTRY(false, LAY_F, LAY_F)};
 
-// entries 40..47: the four-wave kernel with the lean instruction stream (gett_h16v.hip), 48..55: its 16x16x32 form, 56..63: the
-// 128 x 128 mid-size sibling of that (two workgroups per CU), 64..71 / 72..79: that tile on a four-deep ring / with dedicated
-// data-moving waves, 80..87: the 64 x 64 tile, 88..95: the persistent 256 x 256 kernel (gett_h16p.hip, round 5); same order
+// The whole family in the order of H16Variant (launch.h), which names each variant's first entry: this file's five, then gett_h16v.hip's
+// table (H16_W4V: the lean instruction stream, H16_W4X: its 16x16x32 form, H16_W4M / H16_W4M4 / H16_W8M: the 128 x 128 tile, H16_W4Q: the
+// 64 x 64 tile), then H16_W4P, the persistent 256 x 256 kernel (gett_h16p.hip, round 5); eight entries each, same order
 const GettKernelInfo* gett_h16_kernels(int* count) {
     constexpr int nHere = (int)(sizeof(g_h16_table) / sizeof(g_h16_table[0]));
     struct All { GettKernelInfo e[nHere + 56 + 8]; int n; };
@@ -1432,7 +1432,7 @@ const GettKernelInfo* gett_h16_kernels(int* count) {
         const GettKernelInfo* v = gett_h16v_kernels(&nv);
         a.n = nHere;
         for (int i = 0; i < nv && i < 56; ++i) a.e[a.n++] = v[i];
-        const GettKernelInfo* pk = gett_h16p_kernels(&nv);     // 88..95: the persistent 256 x 256 kernel (gett_h16p.hip)
+        const GettKernelInfo* pk = gett_h16p_kernels(&nv);     // H16_W4P: the persistent 256 x 256 kernel (gett_h16p.hip)
         for (int i = 0; i < nv && i < 8; ++i) a.e[a.n++] = pk[i];
         return a;
     }();

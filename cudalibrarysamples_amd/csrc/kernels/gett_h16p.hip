@@ -704,7 +704,7 @@ static hipError_t launch_h16w4p(const GettParams& p, hipStream_t stream) {
 }
 
 #define CTAMD_H16W4P_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 12, 1, 0, &launch_h16w4p<bf, la, lb>, 0},
+    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 12, 1, 0, &launch_h16w4p<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4p_kernel", H16_W4P},
 static const GettKernelInfo g_h16p_table[] = {
     CTAMD_H16W4P_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4P_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4P_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4P_ENTRY(true, LAY_F, LAY_F)

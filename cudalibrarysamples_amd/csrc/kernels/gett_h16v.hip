@@ -1611,47 +1611,47 @@ static hipError_t launch_h16w4v(const GettParams& p, hipStream_t stream) {
 
 // bf16 entries first, then fp16, each in the order (layA, layB) = (K,K) (K,F) (F,K) (F,F) — the order of gett_h16.hip's table
 #define CTAMD_H16W4V_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 6, 1, 0, &launch_h16w4v<bf, la, lb>, 0},
+    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 6, 1, 0, &launch_h16w4v<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4v_kernel", H16_W4V},
 #else
 static hipError_t launch_h16v_not_built(const GettParams&, hipStream_t) { return hipErrorNotSupported; }
-#define CTAMD_H16W4V_ENTRY(bf, la, lb) {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 6, 1, 2, &launch_h16v_not_built, 0},
+#define CTAMD_H16W4V_ENTRY(bf, la, lb) {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 6, 1, 2, &launch_h16v_not_built, 0, 0, 0, 0, "gett_h16w4v_kernel", H16_W4V},
 #endif
 #define CTAMD_H16W4X_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 7, 1, 0, &launch_h16w4x<bf, la, lb>, 0},
+    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 7, 1, 0, &launch_h16w4x<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4x_kernel", H16_W4X},
 #define CTAMD_H16W4M_ENTRY(bf, la, lb) \
-    {kMTile, kMTile, kHBK, 2, 2, 1, la, lb, 256, 8, 1, 0, &launch_h16w4m<bf, la, lb, 2>, 0},
+    {kMTile, kMTile, kHBK, 2, 2, 1, la, lb, 256, 8, 1, 0, &launch_h16w4m<bf, la, lb, 2>, 0, 0, 0, 0, "gett_h16w4m_kernel", H16_W4M},
 #define CTAMD_H16W4M4_ENTRY(bf, la, lb) \
-    {kMTile, kMTile, kHBK, 2, 2, 1, la, lb, 256, 9, 1, 0, &launch_h16w4m<bf, la, lb, 4>, 0},
+    {kMTile, kMTile, kHBK, 2, 2, 1, la, lb, 256, 9, 1, 0, &launch_h16w4m<bf, la, lb, 4>, 0, 0, 0, 0, "gett_h16w4m4_kernel", H16_W4M4},
 #define CTAMD_H16W8M_ENTRY(bf, la, lb) \
-    {kMTile, kMTile, kHBK, 2, 2, 1, la, lb, 512, 10, 1, 0, &launch_h16w8m<bf, la, lb>, 0},
+    {kMTile, kMTile, kHBK, 2, 2, 1, la, lb, 512, 10, 1, 0, &launch_h16w8m<bf, la, lb>, 0, 0, 0, 0, "gett_h16w8m_kernel", H16_W8M},
 #define CTAMD_H16W4Q_ENTRY(bf, la, lb) \
-    {kQTile, kQTile, kHBK, 2, 2, 1, la, lb, 256, 11, 1, 0, &launch_h16w4q<bf, la, lb>, 0},
+    {kQTile, kQTile, kHBK, 2, 2, 1, la, lb, 256, 11, 1, 0, &launch_h16w4q<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4q_kernel", H16_W4Q},
 static const GettKernelInfo g_h16v_table[] = {
     CTAMD_H16W4V_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4V_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4V_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4V_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4V_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4V_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4V_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4V_ENTRY(false, LAY_F, LAY_F)
-    // entries 8..15 of this table (48..55 of the 16-bit family): the 16x16x32 form
+    // H16_W4X: the 16x16x32 form
     CTAMD_H16W4X_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4X_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4X_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4X_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4X_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4X_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4X_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4X_ENTRY(false, LAY_F, LAY_F)
-    // entries 16..23 (56..63 of the family): the 128 x 128 mid-size sibling, two workgroups per CU
+    // H16_W4M: the 128 x 128 mid-size sibling, two workgroups per CU
     CTAMD_H16W4M_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4M_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4M_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4M_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4M_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4M_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4M_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4M_ENTRY(false, LAY_F, LAY_F)
-    // entries 24..31 (64..71 of the family): the same with a four-deep K-tile ring, one workgroup per CU
+    // H16_W4M4: the same with a four-deep K-tile ring, one workgroup per CU
     CTAMD_H16W4M4_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4M4_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4M4_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4M4_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4M4_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4M4_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4M4_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4M4_ENTRY(false, LAY_F, LAY_F)
-    // entries 32..39 (72..79 of the family): 128 x 128, four multiplying + four data-moving waves, four-deep ring
+    // H16_W8M: 128 x 128, four multiplying + four data-moving waves, four-deep ring
     CTAMD_H16W8M_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W8M_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W8M_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W8M_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W8M_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W8M_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W8M_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W8M_ENTRY(false, LAY_F, LAY_F)
-    // entries 40..47 (80..87 of the family): 64 x 64, four waves, four-deep ring of 16-KiB K-tiles, two workgroups per CU
+    // H16_W4Q: 64 x 64, four waves, four-deep ring of 16-KiB K-tiles, two workgroups per CU
     CTAMD_H16W4Q_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4Q_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4Q_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4Q_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4Q_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4Q_ENTRY(false, LAY_K, LAY_F)

@@ -12,12 +12,29 @@ enum OperandLayout : int {
     LAY_S = 2   // arbitrary strides: 4-byte gathers
 };
 
+// Variants of the aligned 16-bit family, gett_h16<name>_kernel.  gett_h16_kernels() holds eight entries per variant — bf16 first, then
+// fp16, each in the order (layA, layB) = (K,K) (K,F) (F,K) (F,F) — and a variant's value is the table position of its first entry: the
+// table's order and length are fixed (kernel indices are written into plan-cache files), and this is where the order is written down.
+enum H16Variant : int {
+    H16_W8 = 0, H16_W4 = 8, H16_S = 16, H16_W4S = 24, H16_W4R = 32, H16_W4V = 40,   // retired families (research builds): eight waves in two
+                     // ping-pong rows; four waves, one per SIMD; eight / four free-running waves on a K-tile-32 ring; four waves
+                     // register-staged; four waves with the lean instruction stream (gett_h16v.hip)
+    H16_W4X  = 48,   // the lean four-wave kernel on the 16x16x32 MFMA: the default 256 x 256 kernel
+    H16_W4M  = 56,   // 128 x 128 on a two-deep ring, two workgroups per CU
+    H16_W4M4 = 64,   // 128 x 128 on a four-deep ring, one workgroup per CU
+    H16_W8M  = 72,   // 128 x 128, four multiplying + four data-moving waves
+    H16_W4Q  = 80,   // 64 x 64, two workgroups per CU (also the strip kernel of a strip plan)
+    H16_W4P  = 88    // the persistent 256 x 256 kernel (gett_h16p.hip); its one-tile twin is H16_W4X
+};
+constexpr int h16_entry(H16Variant variant, int layoutIdx) { return (int)variant + layoutIdx; }   // layoutIdx 0..7
+
 struct GettKernelInfo {
     int bm, bn, bk;      // workgroup tile
     int wm, wn, wk;      // wave grid inside the workgroup
     int layA, layB;      // OperandLayout of kernel-A / kernel-B
     int threads;
-    int pf;              // K-tiles in flight in registers
+    int pf;              // fp32 family: K-tiles in flight (registers, or the depth of the LDS ring); 16-bit and general families: a code
+                         // that tools read from ctamdDescribePlan and nothing in the library tests — identity is `name` / `variant`
     int kfast;           // 1: requires extent(fastest K mode) % bk == 0
     int ablation;        // != 0: measurement-only variant (wrong results), never ranked by default
     hipError_t (*launch)(const GettParams&, hipStream_t);
@@ -27,6 +44,8 @@ struct GettKernelInfo {
                          //    problems that read every operand byte once and whose operands exceed the Infinity Cache anyway
     int elem;            // general family (gett_gen_kernels): GenElem of the instantiation
     int vec;             // general family: elements per staged unit = per global load (both operands)
+    const char* name;    // the __global__ template the entry launches (ctamdDescribePlan's "kname")
+    int variant;         // aligned 16-bit family: H16Variant of the entry (0 in the other families' tables)
 };
 
 // element types of the general MFMA family (gett_gen.inc)
@@ -47,8 +66,8 @@ const GettKernelInfo* gett_f32_stream_kernels(int* count);
 
 // bf16 / fp16 data, fp32 accumulation (v_mfma_f32_32x32x16_{bf16,f16}), gett_h16.hip
 const GettKernelInfo* gett_h16_kernels(int* count);
-const GettKernelInfo* gett_h16v_kernels(int* count);   // gett_h16v.hip: appended to the table above as entries 40..87
-const GettKernelInfo* gett_h16p_kernels(int* count);   // gett_h16p.hip (persistent 256 x 256 kernel): entries 88..95
+const GettKernelInfo* gett_h16v_kernels(int* count);   // gett_h16v.hip: appended to the table above, H16_W4V .. H16_W4Q
+const GettKernelInfo* gett_h16p_kernels(int* count);   // gett_h16p.hip (persistent 256 x 256 kernel): H16_W4P
 
 // general MFMA family: bf16 / fp16 shapes the aligned kernels above refuse (no 16-byte lanes, K not in whole 64-deep tiles), fp64,
 // complex64 / complex128 — register-staged, any strides and extents (gett_gen.inc; the table is the concatenation of the three
