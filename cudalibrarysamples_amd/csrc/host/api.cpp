@@ -2196,8 +2196,20 @@ cutensorStatus_t cutensorElementwiseTrinaryExecute(const cutensorHandle_t handle
         q.alpha = (float)a; q.alpha64 = a; q.xi = (float)b; q.xi64 = b; q.gamma = (float)g; q.gamma64 = g;
         err = launch_elementwise(q, t.last.variant, (int)plan->dtype, stream);
     } else if (t.twoPass) {
-        err = run_elementwise(t.first, plan->dtype, a, A, 0.0, nullptr, D, stream);                       // D = alpha perm(A)
-        if (err == hipSuccess) err = run_elementwise(t.last, plan->dtype, b, B, g, C, D, stream, D, 1.0);  // combine in place
+        // C inside D's range (in-place use: C == D) and read by the last pass: pass 1 would overwrite it first.  One launch of the
+        // element-gather kernel instead — a lane reads its element of C before it writes that element of D.
+        const uintptr_t c = reinterpret_cast<uintptr_t>(C), d = reinterpret_cast<uintptr_t>(D);
+        const bool readsC = t.last.usesC && (g != 0.0 || (t.last.p.opAC != 0 && t.last.p.opAC != CUTENSOR_OP_ADD));
+        if (readsC && c < d + t.spanD && d < c + t.spanC) {
+            if (!t.hasGather) return CUTENSOR_STATUS_NOT_SUPPORTED;   // (more unfusable modes than the single launch describes)
+            Ew2DParams q = t.gather.p;
+            q.A = A; q.X = B; q.C = C; q.D = D; q.E = nullptr;
+            q.alpha = (float)a; q.alpha64 = a; q.xi = (float)b; q.xi64 = b; q.gamma = (float)g; q.gamma64 = g;
+            err = launch_elementwise(q, EW_GENERIC, (int)plan->dtype, stream);
+        } else {
+            err = run_elementwise(t.first, plan->dtype, a, A, 0.0, nullptr, D, stream);                       // D = alpha perm(A)
+            if (err == hipSuccess) err = run_elementwise(t.last, plan->dtype, b, B, g, C, D, stream, D, 1.0);  // combine in place
+        }
     } else if (t.swapAB) {
         err = run_elementwise(t.last, plan->dtype, a, A, g, C, D, stream, B, b);   // E = B (has D's layout)
     } else {
@@ -2382,9 +2394,18 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
                                (long long)plan->view.K[i].sA, (long long)plan->view.K[i].sB);
         if (n > 0 && (size_t)n < len) n += std::snprintf(buf + n, len - n, "]}");
     } else if (plan->kind == OpKind::Reduction && !plan->red.isPermutation) {
-        n = std::snprintf(buf, len, "{\"op\":\"reduction\",\"variant\":%d,\"kept\":%u,\"red\":%u,\"splitR\":%u,\"workspace\":%llu}",
-                          plan->red.variant, plan->red.p.kept.total, plan->red.p.red.total, plan->red.p.splitR,
-                          (unsigned long long)plan->requiredWorkspace);
+        n = std::snprintf(buf, len, "{\"op\":\"reduction\",\"variant\":%d,\"kept\":%u,\"red\":%u,\"splitR\":%u,\"redPerSplit\":%u,\"rowAny\":%u,\"workspace\":%llu}",
+                          plan->red.variant, plan->red.p.kept.total, plan->red.p.red.total, plan->red.p.splitR, plan->red.p.redPerSplit,
+                          plan->red.p.rowAny, (unsigned long long)plan->requiredWorkspace);
+    } else if (plan->kind == OpKind::ElementwiseTrinary) {
+        // the three forms (plan_elementwise_trinary): one pass with E, one pass with two tiles, two passes (variant_first: pass 1's kernel;
+        // variant_inplace: the single launch that replaces both passes when C overlaps D, -1 if there is none).  "op" stays "elementwise",
+        // as for every plan of the element-wise family; "form" tells the trinary plans from the others
+        const EwTrinaryPlan& t = plan->ew3;
+        n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"form\":\"trinary\",\"passes\":%d,\"bothPermuted\":%d,\"swapAB\":%d,\"variant\":%d,\"variant_first\":%d,"
+                          "\"variant_inplace\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u}",
+                          t.twoPass ? 2 : 1, (int)t.bothPermuted, (int)t.swapAB, t.last.variant, t.twoPass ? t.first.variant : -1,
+                          t.hasGather ? t.gather.variant : -1, t.last.p.E0, t.last.p.E1, t.last.p.rest.total, t.last.p.nBlocks, t.last.p.tile0);
     } else {
         const EwPlan& e = (plan->kind == OpKind::Reduction) ? plan->red.perm : plan->ew;
         n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u,\"order\":%u}",

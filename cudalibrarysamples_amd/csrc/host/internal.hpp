@@ -170,6 +170,12 @@ struct EwTrinaryPlan {
     bool   bothPermuted = false; // single pass with two LDS tiles: A through the tile path, B as the second tile operand
     EwPlan first;                // permutation X1 -> D (two-pass form only)
     EwPlan last;
+    // two-pass form with C overlapping D (in-place use, as elementwise_binary.cu:202-205 passes C = D): pass 1 would overwrite C before
+    // the last pass reads it, so such a call runs `gather` instead — ONE launch of the element-gather kernel with A on its tile path and
+    // B as X, where every lane reads its own element of C before it writes that element of D
+    bool     hasGather = false;
+    EwPlan   gather;
+    uint64_t spanC = 0, spanD = 0;   // bytes from the first to one past the last element of C / D
 };
 struct ReducePlan {
     int          variant = RED_GENERIC;

@@ -377,7 +377,8 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
         both.A = op.A;            // tile path
         both.B = op.B;            // second tile (X)
         EwPlan one;
-        if (plan_elementwise(both, one, nullptr, false) == CUTENSOR_STATUS_SUCCESS && one.usesX && one.variant == EW_TRANSPOSE) {
+        const bool oneOK = plan_elementwise(both, one, nullptr, false) == CUTENSOR_STATUS_SUCCESS && one.usesX;
+        if (oneOK && one.variant == EW_TRANSPOSE) {
             plan.twoPass = false;
             plan.bothPermuted = true;
             plan.last = one;
@@ -386,6 +387,16 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
             return CUTENSOR_STATUS_SUCCESS;
         }
         plan.twoPass = true;
+        // the single-launch form for a C that overlaps D (EwTrinaryPlan::gather): with a second permuted operand the planner offers the
+        // two-tile transposition or the element-gather kernel, and the former was refused above
+        if (oneOK && one.variant == EW_GENERIC) {
+            plan.hasGather = true;
+            plan.gather = one;
+            plan.gather.p.opAB = (int32_t)op.opAB;
+            plan.gather.p.opAC = (int32_t)op.opReduce;
+        }
+        plan.spanC = (uint64_t)op.C.desc.numElementsSpanned() * (uint64_t)dtype_size(op.C.desc.dtype);
+        plan.spanD = (uint64_t)op.D.desc.numElementsSpanned() * (uint64_t)dtype_size(op.D.desc.dtype);
         cutensorOperationDescriptor first = op;
         first.kind = OpKind::Permutation;
         first.C = TensorUse{};

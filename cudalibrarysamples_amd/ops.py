@@ -178,9 +178,9 @@ def permutation_plan(handle, extA, modesA, extB, modesB, dtype=ct.R_32F, strideA
 
 
 def binary_plan(handle, extA, modesA, extC, modesC, op="ADD", dtype=ct.R_32F, compute=None, alignment=128, opA=ct.OP_IDENTITY,
-                opC=ct.OP_IDENTITY, **plan_kw):
+                opC=ct.OP_IDENTITY, strideA=None, strideC=None, **plan_kw):
     """D = op(alpha * perm(A), gamma * C) — cutensorCreateElementwiseBinary (elementwise_binary.cu:149-153)."""
-    dA, dC = _desc3(handle, [(extA, None), (extC, None)], dtype, alignment)
+    dA, dC = _desc3(handle, [(extA, strideA), (extC, strideC)], dtype, alignment)
     opd = ctypes.c_void_p()
     st = ct.cutensorCreateElementwiseBinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), opA, dC, ct.i32(modesC),
                                             opC, dC, ct.i32(modesC), _OPS[op],
@@ -193,10 +193,10 @@ def binary_plan(handle, extA, modesA, extC, modesC, op="ADD", dtype=ct.R_32F, co
 
 
 def trinary_plan(handle, extA, modesA, extB, modesB, extC, modesC, extD, modesD, opAB="ADD", opABC="ADD", dtype=ct.R_32F,
-                 compute=None, alignment=128, **plan_kw):
+                 compute=None, alignment=128, strideA=None, strideB=None, strideC=None, strideD=None, **plan_kw):
     """D = opABC(opAB(alpha * perm(A), beta * perm(B)), gamma * perm(C)) — cutensorCreateElementwiseTrinary
     (elementwise_trinary.cu:174-182)."""
-    dA, dB, dC, dD = _desc3(handle, [(extA, None), (extB, None), (extC, None), (extD, None)], dtype, alignment)
+    dA, dB, dC, dD = _desc3(handle, [(extA, strideA), (extB, strideB), (extC, strideC), (extD, strideD)], dtype, alignment)
     opd = ctypes.c_void_p()
     st = ct.cutensorCreateElementwiseTrinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), ct.OP_IDENTITY, dB, ct.i32(modesB),
                                              ct.OP_IDENTITY, dC, ct.i32(modesC), ct.OP_IDENTITY, dD, ct.i32(modesD),

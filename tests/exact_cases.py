@@ -266,19 +266,19 @@ ROWS_SWEEP = [(dict(m=m_, n=n_, k=k_), mA, mB, "mn") for (mA, mB) in LAYOUTS for
 class Placed:
     """extents (first fastest), the first mode's pitch padded by `pad`, at element offset `off` behind a 256-byte-aligned guard"""
 
-    def __init__(self, extents, dtype, pad=0, off=0):
+    def __init__(self, extents, dtype, pad=0, off=0, strides=None):
         import torch
         import guarded as gd
         self.extents = list(extents)
         self.tdt = xd.TORCH_DTYPES[dtype]
         self.es = torch.empty((), dtype=self.tdt).element_size()
-        self.strides = gd.packed_strides(self.extents, pad)
+        self.strides = list(strides) if strides is not None else gd.packed_strides(self.extents, pad)     # (strides: any padded pitches)
         span = 1 + sum((e - 1) * s for e, s in zip(self.extents, self.strides)) if self.extents else 1
         self.start = GUARD + off
         self.raw = torch.full(((2 * GUARD + off + span) * self.es,), 0xFF, dtype=torch.uint8, device="cuda")     # 0xFF..: a NaN in every type
         self.buf = self.raw.view(self.tdt)
         self.ptr = self.buf.data_ptr() + self.start * self.es
-        self.packed = pad == 0
+        self.packed = pad == 0 and strides is None
 
     def view(self):
         rev = lambda x: list(reversed(x)) or [1]   # noqa: E731
@@ -490,14 +490,14 @@ def _stop(why):
     pytest.exit(why, returncode=3)
 
 
-def in_child(ids, env, timeout, mode="run"):
-    """`python exact_cases.py MODE ids...` in a fresh process with its own time limit; returns the child's output"""
+def in_child(ids, env, timeout, mode="run", script="exact_cases.py"):
+    """`python exact_cases.py MODE ids...` (or another case table's script) in a fresh process with its own time limit; returns the child's output"""
     import subprocess
     here = os.path.dirname(os.path.abspath(__file__))
     root = os.path.dirname(here)
     child_env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, here]), **env)
     try:
-        r = subprocess.run([sys.executable, os.path.join(here, "exact_cases.py"), mode] + list(ids), capture_output=True, text=True, timeout=timeout,
+        r = subprocess.run([sys.executable, os.path.join(here, script), mode] + list(ids), capture_output=True, text=True, timeout=timeout,
                            env=child_env, cwd=root)
     except subprocess.TimeoutExpired as e:
         _stop("a child (%s %s) ran into its time limit of %d s\n%s" % (mode, env, timeout, (e.stdout or b"")[-2000:]))

@@ -103,17 +103,21 @@ def test_block_permutation_bit_exact_at_alpha_one(env, dtype_name):
     (dict(n=5, i=4, j=6), "jin", "ij", 2),                  # einsum.cu:451 "nij->ji" reversed
     # round 6: odd extents with A's stride-1 mode REDUCED -> the element-gather variant's wave-per-kept-element form (reduce_row_any_kernel)
     (dict(a=77, b=5, c=3), "abc", "bc", 2),                 # 77 reduced elements per kept one: two passes of a wave, ragged
-    (dict(a=4099, b=3), "ab", "b", 2),                      # three kept elements: the reduced range is split, partials + finalize
+    (dict(a=4099, b=3), "ab", "b", 2),                      # three kept elements, one split (the wave-per-kept-element form splits from 8192 reduced elements)
     (dict(a=131, b=9, c=7), "abc", "c", 2),                 # two reduced modes (a, b), the walk crosses the mode boundary
     (dict(a=131, b=67, c=5), "abc", "ac", 2),               # stride-1 mode kept, 67 reduced rows: the unrolled loop and its tails
+    (dict(a=8195, b=3), "ab", "b", 2, "split"),             # three kept elements: the reduced range is split, partials + finalize
+    (dict(a=16388, b=3), "ab", "b", 1, "split"),            # ... and RED_ROW, which splits from 16384 reduced elements
 ])
 def test_reduction(env, case):
     ct, ops, h, torch = env
-    ext, mA, mC, variant = case
+    ext, mA, mC, variant, *split = case
     eA, eC = [ext[c] for c in mA], [ext[c] for c in mC]
     A, C = make_tensor(eA, 21), make_tensor(eC, 22)
     p = ops.reduction_plan(h, eA, mA, eC, mC)
     assert p.describe()["variant"] == variant, p.describe()
+    if split:
+        assert p.describe()["splitR"] > 1 and p.required_workspace > 0, p.describe()
     assert p.required_workspace <= p.workspace_estimate
     dA, dC = to_device(A), to_device(C)
     ws = torch.empty(max(p.required_workspace, 16), dtype=torch.uint8, device="cuda")
@@ -399,19 +403,23 @@ def test_complex_permutation(env, dtype, case):
     (dict(m=40, h=16, k=8, v=12), "mhkv", "mv"),
     (dict(a=64, b=40, c=24), "abc", "ac"),         # the unary einsum "cba->ca" of the reference's binding
     (dict(a=64, b=40, c=24), "abc", "c"),
-    (dict(a=4096, b=6), "ab", "b"),                # few kept elements: the reduced range is split over workgroups + finalize
+    (dict(a=4096, b=6), "ab", "b"),                # few kept elements, one split (RED_ROW splits from 16384 reduced elements)
     (dict(a=64, b=48), "ab", ""),                  # full reduction to a scalar
+    (dict(a=16388, b=3), "ab", "b", "split"),      # few kept elements: the reduced range is split over workgroups + finalize
+    (dict(a=33, b=131), "ab", "a", "split"),       # odd extents: the element-gather kernel (complex128: RED_COL), split + the complex finalize
 ])
 def test_complex_reduction(env, dtype, case):
     ct, ops, h, torch = env
     np_dt, cname, rtol = CPLX[dtype]
-    ext, mA, mC = case
+    ext, mA, mC, *split = case
     eA, eC = [ext[c] for c in mA], [ext[c] for c in mC]
     A, C = _cplx(eA, 71, np_dt), _cplx(eC, 72, np_dt)
     dA, dC = _cdev(torch, A), _cdev(torch, C)
     for alpha, beta, cA, cC in ((1.0, 0.0, False, False), (1.1 - 0.3j, 0.5j, False, False), (-1j, 2.0, True, True)):
         p = ops.reduction_plan(h, eA, mA, eC, mC, dtype=getattr(ct, cname), opA=ct.OP_CONJ if cA else ct.OP_IDENTITY,
                                opC=ct.OP_CONJ if cC else ct.OP_IDENTITY)
+        if split:
+            assert p.describe()["splitR"] > 1 and p.required_workspace > 0, p.describe()
         assert p.required_workspace <= p.workspace_estimate
         ws = torch.empty(max(p.required_workspace, 16), dtype=torch.uint8, device="cuda")
         dD = dC.clone()

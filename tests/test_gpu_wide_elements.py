@@ -114,8 +114,9 @@ def test_padded_strides_keep_the_tiled_kernels_and_leave_the_padding_alone(env):
 REDS = [  # extents, modes of A, kept modes, expected variant
     (dict(a=64, b=40, c=24), "abc", "ac", RED_COL),
     (dict(a=64, b=40, c=24), "abc", "c", RED_ROW),
-    (dict(a=2048, b=6), "ab", "b", RED_ROW),         # few kept elements: split over workgroups + finalize
-    (dict(a=16, b=3000), "ab", "a", RED_COL),        # few kept elements, long strided reduction: split
+    (dict(a=2048, b=6), "ab", "b", RED_ROW),         # few kept elements, one split (RED_ROW splits from 16384 reduced elements)
+    (dict(x=16392, b=3), "xb", "b", RED_ROW, "split"),      # few kept elements: split over workgroups + finalize
+    (dict(a=16, b=3000), "ab", "a", RED_COL, "split"),      # few kept elements, long strided reduction: split
     (dict(m=40, h=16, k=8, v=12), "mhkv", "mv", RED_COL),
     (dict(a=64, b=48), "ab", "", RED_ROW),           # full reduction to a scalar
 ]
@@ -126,7 +127,7 @@ REDS = [  # extents, modes of A, kept modes, expected variant
 def test_tiled_reductions(env, dtype, case):
     ct, ops, h, torch = env
     np_dt, cname, rtol, cx = DT[dtype]
-    ext, mA, mC, variant = case
+    ext, mA, mC, variant, *split = case
     eA, eC = [ext[c] for c in mA], [ext[c] for c in mC]
     A, C = _rand(eA, 31, np_dt, cx), _rand(eC, 32, np_dt, cx)
     dA, dC = _dev(torch, A), _dev(torch, C)
@@ -135,6 +136,8 @@ def test_tiled_reductions(env, dtype, case):
         p = ops.reduction_plan(h, eA, mA, eC, mC, dtype=getattr(ct, cname), opA=ct.OP_CONJ if cA else ct.OP_IDENTITY,
                                opC=ct.OP_CONJ if cC else ct.OP_IDENTITY, workspace_limit=1 << 26)
         assert p.describe()["variant"] == variant, p.describe()
+        if split:
+            assert p.describe()["splitR"] > 1 and p.required_workspace > 0, p.describe()
         assert p.required_workspace <= p.workspace_estimate
         ws = torch.empty(max(p.required_workspace, 16), dtype=torch.uint8, device="cuda")
         dD = dC.clone()
@@ -150,6 +153,8 @@ def test_tiled_reductions(env, dtype, case):
         for opname, fn in (("OP_MAX", np.max), ("OP_MIN", np.min)):
             p = ops.reduction_plan(h, eA, mA, eC, mC, dtype=getattr(ct, cname), op_reduce=getattr(ct, opname), workspace_limit=1 << 26)
             assert p.describe()["variant"] == variant
+            if split:
+                assert p.describe()["splitR"] > 1, p.describe()
             ws = torch.empty(max(p.required_workspace, 16), dtype=torch.uint8, device="cuda")
             dD = torch.zeros(max(int(np.prod(eC)), 1), dtype=dA.dtype, device="cuda")
             p.reduce(1.0, dA.data_ptr(), 0.0, dD.data_ptr(), dD.data_ptr(), ws.data_ptr(), p.required_workspace, 0)
@@ -165,13 +170,14 @@ def test_tiled_reductions(env, dtype, case):
 @pytest.mark.parametrize("case", [
     (dict(a=64, b=40, c=24), "abc", "ac", RED_COL),
     (dict(a=64, b=40, c=24), "abc", "c", RED_ROW),
-    (dict(a=4096, b=6), "ab", "b", RED_ROW),
-    (dict(a=16, b=3000), "ab", "a", RED_COL),
+    (dict(a=16392, b=3), "ab", "b", RED_ROW, "split"),       # (RED_ROW splits from 16384 reduced elements)
+    (dict(a=16, b=3000), "ab", "a", RED_COL, "split"),
     (dict(a=128, b=48), "ab", "", RED_ROW),
-], ids=["ac", "c", "b-split", "a-split", "scalar"])
+    (dict(a=4096, b=6), "ab", "b", RED_ROW),                 # few kept elements, one split
+], ids=["ac", "c", "b-split", "a-split", "scalar", "b-row"])
 def test_16_bit_reductions_accumulate_in_fp32(env, dtype, case):
     ct, ops, h, torch = env
-    ext, mA, mC, variant = case
+    ext, mA, mC, variant, *split = case
     eA, eC = [ext[c] for c in mA], [ext[c] for c in mC]
     tdt = getattr(torch, dtype)
     cdt = ct.R_16BF if dtype == "bfloat16" else ct.R_16F
@@ -185,6 +191,8 @@ def test_16_bit_reductions_accumulate_in_fp32(env, dtype, case):
     for alpha, beta in ((1.0, 0.0), (1.1, -0.5)):
         p = ops.reduction_plan(h, eA, mA, eC, mC, dtype=cdt, workspace_limit=1 << 26)
         assert p.describe()["variant"] == variant, p.describe()
+        if split:
+            assert p.describe()["splitR"] > 1 and p.required_workspace > 0, p.describe()
         ws = torch.empty(max(p.required_workspace, 16), dtype=torch.uint8, device="cuda")
         dD = dC.clone()
         p.reduce(alpha, dA.data_ptr(), beta, dD.data_ptr(), dD.data_ptr(), ws.data_ptr(), p.required_workspace, 0)
