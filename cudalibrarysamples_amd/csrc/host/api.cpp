@@ -2106,7 +2106,10 @@ static hipError_t run_elementwise(const EwPlan& ew, hipDataType dtype, double a,
     p.alpha = (float)a; p.gamma = (float)g; p.alpha64 = a; p.gamma64 = g;
     p.alphaIm = aIm; p.gammaIm = gIm;
     p.delta = (float)d; p.delta64 = d;
-    return launch_elementwise(p, ew.variant, (int)dtype, stream);
+    // the block kernel moves elements and scales them, nothing else: under a unary operator the plan runs on the kernel its tiles were
+    // laid out for (same variant in the description, as for an attached operand)
+    const int variant = (ew.variant == EW_BLOCK && p.unA != 0) ? ew.blockFrom : ew.variant;
+    return launch_elementwise(p, variant, (int)dtype, stream);
 }
 
 // reduction.cu:219-222, einsum.cu:369-372
@@ -2334,6 +2337,14 @@ void ctamdPlanMemoStats(const cutensorHandle_t handle, uint64_t* hits, uint64_t*
 // buf holds n characters of a plan's own keys, `{"key":..,"key":..,` — the keys of its inner plan follow: the inner plan's description is
 // written over the trailing ',' and its '{' turned into that ','
 static int describe_inner(const cutensorPlan& plan, char* buf, size_t len, int n);
+// A plan of the element-wise or reduction family whose operands carry a unary operator other than IDENTITY / CONJ: the closing '}' of the
+// description in buf[0, n) becomes ,"unary":[opA, opB, opC]} (cutensorOperator_t values, IDENTITY where there is none).  Every other
+// description stays as it is.
+static int describe_unary(char* buf, size_t len, int n, int32_t a, int32_t b, int32_t c) {
+    if ((a == 0 && b == 0 && c == 0) || n <= 0 || (size_t)n >= len || buf[n - 1] != '}') return n;
+    auto code = [](int32_t u) { return u == 0 ? (int)CUTENSOR_OP_IDENTITY : (int)u; };
+    return n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"unary\":[%d,%d,%d]}", code(a), code(b), code(c));
+}
 // Writes a one-line JSON description of the plan's kernel choice into buf.
 int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     if (plan == nullptr || buf == nullptr || len == 0) return -1;
@@ -2397,6 +2408,7 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
         n = std::snprintf(buf, len, "{\"op\":\"reduction\",\"variant\":%d,\"kept\":%u,\"red\":%u,\"splitR\":%u,\"redPerSplit\":%u,\"rowAny\":%u,\"workspace\":%llu}",
                           plan->red.variant, plan->red.p.kept.total, plan->red.p.red.total, plan->red.p.splitR, plan->red.p.redPerSplit,
                           plan->red.p.rowAny, (unsigned long long)plan->requiredWorkspace);
+        n = describe_unary(buf, len, n, plan->red.p.unA, 0, plan->red.p.unC);
     } else if (plan->kind == OpKind::ElementwiseTrinary) {
         // the three forms (plan_elementwise_trinary): one pass with E, one pass with two tiles, two passes (variant_first: pass 1's kernel;
         // variant_inplace: the single launch that replaces both passes when C overlaps D, -1 if there is none).  "op" stays "elementwise",
@@ -2406,10 +2418,16 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
                           "\"variant_inplace\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u}",
                           t.twoPass ? 2 : 1, (int)t.bothPermuted, (int)t.swapAB, t.last.variant, t.twoPass ? t.first.variant : -1,
                           t.hasGather ? t.gather.variant : -1, t.last.p.E0, t.last.p.E1, t.last.p.rest.total, t.last.p.nBlocks, t.last.p.tile0);
+        // each operand's operator, read back from the role its form gave it
+        const Ew2DParams& q = t.last.p;
+        const int32_t uA = t.bothPermuted ? q.unA : t.twoPass ? t.first.p.unA : t.swapAB ? q.unA : q.unE;
+        const int32_t uB = t.bothPermuted ? q.unX : t.twoPass ? q.unA : t.swapAB ? q.unE : q.unA;
+        n = describe_unary(buf, len, n, uA, uB, q.unC);
     } else {
         const EwPlan& e = (plan->kind == OpKind::Reduction) ? plan->red.perm : plan->ew;
         n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u,\"order\":%u}",
                           e.variant, e.p.E0, e.p.E1, e.p.rest.total, e.p.nBlocks, e.p.tile0, e.p.order);
+        n = describe_unary(buf, len, n, e.p.unA, 0, e.p.unC);
     }
     return n;
 } CTAMD_API_CATCH_INT

@@ -161,6 +161,9 @@ struct EwPlan {
     Ew2DParams p{};              // pointers / scalars are filled at launch
     bool       usesC = false;
     bool       usesX = false;    // second permuted operand (trinary, both operands permuted)
+    // variant EW_BLOCK: the variant the tile decomposition in p was laid out for (EW_GENERIC, or EW_TRANSPOSE when the block form was
+    // preferred to mostly empty transposing tiles) — what runs when the block kernel cannot serve the launch (a unary operator on A)
+    int        blockFrom = EW_GENERIC;
 };
 // cutensorElementwiseTrinaryExecute: D = opABC(opAB(alpha A, beta B), gamma C) as one or two passes of the
 // element-wise kernels (plan_elementwise_trinary)

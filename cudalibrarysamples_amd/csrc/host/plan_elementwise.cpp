@@ -52,6 +52,23 @@ void fuse(std::vector<EwMode>& g, bool useC) {
     g.swap(out);
 }
 
+// Unary operator of an operand (kernels/unary_op.h): IDENTITY / CONJ on every data type; SQRT, RELU, RCP, SIGMOID, TANH, EXP, LOG, ABS and
+// NEG on real floating-point data.  Returns nullptr when the operator is admitted, else why it is not.
+bool unary_is_plain(cutensorOperator_t o) { return o == CUTENSOR_OP_IDENTITY || o == CUTENSOR_OP_CONJ; }
+const char* unary_refusal(cutensorOperator_t o, hipDataType dtype) {
+    if (unary_is_plain(o)) return nullptr;
+    switch (o) {
+        case CUTENSOR_OP_SQRT: case CUTENSOR_OP_RELU: case CUTENSOR_OP_RCP: case CUTENSOR_OP_SIGMOID: case CUTENSOR_OP_TANH:
+        case CUTENSOR_OP_EXP: case CUTENSOR_OP_LOG: case CUTENSOR_OP_ABS: case CUTENSOR_OP_NEG: break;
+        default: return "not a unary operator";
+    }
+    if (dtype == HIP_C_32F || dtype == HIP_C_64F) return "complex data takes the identity and conjugation operators only";
+    if (dtype != HIP_R_32F && dtype != HIP_R_64F && dtype != HIP_R_16F && dtype != HIP_R_16BF) return "unary operators need floating-point data";
+    return nullptr;
+}
+// the code a kernel gets: 0 for the operators that leave real data as it is
+int32_t unary_code(cutensorOperator_t o) { return unary_is_plain(o) ? 0 : (int32_t)o; }
+
 bool fill_rest(ModeGroup& g, const std::vector<EwMode>& modes) {
     std::memset(&g, 0, sizeof(g));
     if ((int)modes.size() > kMaxGroupModes) return false;
@@ -92,10 +109,13 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "repeated mode label inside one tensor");
     if (A.desc.dtype != D.desc.dtype || (usesC && C.desc.dtype != D.desc.dtype))
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types");
-    // unary operators: IDENTITY, and CONJ (a no-op on real data)
-    auto unary_ok = [](cutensorOperator_t o) { return o == CUTENSOR_OP_IDENTITY || o == CUTENSOR_OP_CONJ; };
-    if (!unary_ok(A.op) || (usesC && !unary_ok(C.op)) || (usesX && op.B.op != CUTENSOR_OP_IDENTITY))
-        return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "only the identity and conjugation operators are implemented");
+    // unary operators: IDENTITY, CONJ (a no-op on real data), and on real data the nine of kernels/unary_op.h
+    if (const char* r = unary_refusal(A.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
+    if (usesC) if (const char* r = unary_refusal(C.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
+    if (usesX) {
+        if (op.B.op == CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "conjugation of the second permuted operand");
+        if (const char* r = unary_refusal(op.B.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
+    }
     for (int32_t l : A.modes)
         if (find_label(D.modes, l) < 0 && A.desc.extent[find_label(A.modes, l)] != 1)
             return fail(CUTENSOR_STATUS_INVALID_VALUE, "mode of A missing from the output");
@@ -165,6 +185,9 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     if (op.kind == OpKind::ElementwiseBinary) p.opAC = (int32_t)op.opReduce;   // ADD / MUL / MAX / MIN; every other caller adds
     p.conjA = (cplx && A.op == CUTENSOR_OP_CONJ) ? 1 : 0;
     p.conjC = (cplx && usesC && C.op == CUTENSOR_OP_CONJ) ? 1 : 0;
+    p.unA = unary_code(A.op);
+    p.unC = usesC ? unary_code(C.op) : 0;
+    p.unX = usesX ? unary_code(op.B.op) : 0;
     std::vector<EwMode> rest;
     int i1 = -1;
     if (!modes.empty()) {
@@ -239,6 +262,7 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     // ew_block_kernel).  The smallest such n; blocks of at most 32 KiB; a workgroup takes as many blocks as fill ~4 Ki elements.
     // Also preferred to the transposing kernel when its tiles would be mostly padding (dim0 = b = 8, dim1 = d = 40 of a 64 x 64 tile:
     // [d = 40, c, b | a] -> [b, c, d | a] at 0.7-0.9 TB/s, profiles/r06zze_block_permute.jsonl).
+    const int beforeBlock = plan.variant;
     const double tileFill = (double)p.E0 * (double)p.E1 / ((double)((p.E0 + t0 - 1) / t0) * t0 * (double)((p.E1 + t1 - 1) / t1) * t1);
     if ((plan.variant == EW_GENERIC || (plan.variant == EW_TRANSPOSE && tileFill < 0.5)) && op.kind == OpKind::Permutation && !usesC && !usesX && !cplx && (h16 || D.desc.dtype == HIP_R_32F) &&
         op.padLeft.empty() && op.padRight.empty() && modes.size() >= 2) {
@@ -272,6 +296,7 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
                 p.blkVec = v16 ? 1u : 0u;
             }
             plan.variant = EW_BLOCK;
+            plan.blockFrom = beforeBlock;
             break;
         }
     }
@@ -344,10 +369,16 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
     };
     auto ok_op = [](cutensorOperator_t o) { return o == CUTENSOR_OP_ADD || o == CUTENSOR_OP_MUL || o == CUTENSOR_OP_MAX || o == CUTENSOR_OP_MIN; };
     if (!ok_op(op.opAB) || !ok_op(op.opReduce)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "binary operator");
-    if (op.A.op != CUTENSOR_OP_IDENTITY || op.B.op != CUTENSOR_OP_IDENTITY || op.C.op != CUTENSOR_OP_IDENTITY)
-        return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "only the identity operator is implemented");
-    if (op.D.desc.dtype == HIP_C_32F || op.D.desc.dtype == HIP_C_64F)
+    if (op.D.desc.dtype == HIP_C_32F || op.D.desc.dtype == HIP_C_64F) {
+        for (const TensorUse* t : {&op.A, &op.B, &op.C})
+            if (!unary_is_plain(t->op)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, unary_refusal(t->op, op.D.desc.dtype));
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "complex element-wise trinary operations");
+    }
+    // unary operators: IDENTITY and the nine of kernels/unary_op.h; each one follows its operand into whichever role the forms below give it
+    for (const TensorUse* t : {&op.A, &op.B, &op.C}) {
+        if (t->op == CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "conjugation in an element-wise trinary operation");
+        if (const char* r = unary_refusal(t->op, op.D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
+    }
     auto same_layout = [&](const TensorUse& X) {
         if (X.modes.size() != op.D.modes.size() || X.desc.dtype != op.D.desc.dtype) return false;
         for (size_t i = 0; i < op.D.modes.size(); ++i) {
@@ -365,7 +396,7 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
     if (aSame || bSame) {
         plan.twoPass = false;
         plan.swapAB = !aSame;                    // E = B, permuted operand = A
-        last.A = plan.swapAB ? op.A : op.B;
+        last.A = plan.swapAB ? op.A : op.B;          // (with its unary operator; the other operand's goes to E below)
         // E rides along with D's strides and is read with D's lane width: its pointer alignment bounds the vector variants too
         const TensorUse& eop = plan.swapAB ? op.B : op.A;
         if (eop.desc.alignment % 16 != 0) last.D.desc.alignment = std::min<uint32_t>(last.D.desc.alignment, eop.desc.alignment);
@@ -408,6 +439,8 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
     if (st != CUTENSOR_STATUS_SUCCESS) return st;
     plan.last.p.opAB = (int32_t)op.opAB;
     plan.last.p.opAC = (int32_t)op.opReduce;
+    // E: the operand with D's layout carries its own operator; the two-pass form's E is pass 1's output alpha * unA(perm A) — no operator again
+    plan.last.p.unE = plan.twoPass ? 0 : unary_code(plan.swapAB ? op.B.op : op.A.op);
     return CUTENSOR_STATUS_SUCCESS;
 }
 
@@ -423,8 +456,9 @@ cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t 
     if (C.modes != D.modes) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "modes of C and D differ");
     if (C.desc.extent != D.desc.extent) return fail(CUTENSOR_STATUS_INVALID_VALUE, "extents of C and D differ");
     if (A.desc.dtype != D.desc.dtype || C.desc.dtype != D.desc.dtype) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types");
-    auto unary_ok = [](cutensorOperator_t o) { return o == CUTENSOR_OP_IDENTITY || o == CUTENSOR_OP_CONJ; };   // CONJ: a no-op on real data
-    if (!unary_ok(A.op) || !unary_ok(C.op)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "only the identity and conjugation operators are implemented");
+    // unary operators: IDENTITY, CONJ (a no-op on real data), and on real data the nine of kernels/unary_op.h
+    if (const char* r = unary_refusal(A.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
+    if (const char* r = unary_refusal(C.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     const int rop = (int)op.opReduce;
     if (rop != CUTENSOR_OP_ADD && rop != CUTENSOR_OP_MUL && rop != CUTENSOR_OP_MAX && rop != CUTENSOR_OP_MIN)
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "reduction operator");
@@ -484,6 +518,8 @@ cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t 
     p.op = rop;
     p.conjA = (cplx && A.op == CUTENSOR_OP_CONJ) ? 1 : 0;
     p.conjC = (cplx && C.op == CUTENSOR_OP_CONJ) ? 1 : 0;
+    p.unA = unary_code(A.op);
+    p.unC = unary_code(C.op);
 
     const bool acc64 = (op.compute != nullptr && op.compute->id == 5 /*64F*/) || A.desc.dtype == HIP_R_64F;
     const bool aligned = A.desc.alignment % 16 == 0;

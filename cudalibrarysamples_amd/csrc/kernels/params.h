@@ -162,6 +162,11 @@ struct Ew2DParams {
     int64_t     sX0, sX1;
     int64_t     restX[kMaxGroupModes];
     float       xi;
+    // Unary operator of each operand on real data (cutensorOperator_t: SQRT / RELU / RCP / SIGMOID / TANH / EXP / LOG / ABS / NEG; 0,
+    // IDENTITY and CONJ leave the element as it is — unary_op.h): applied to the loaded element before its scalar, D = opAC(opAB(delta *
+    // unE(E), alpha * unA(perm A)) [, xi * unX(perm X)], gamma * unC(C)).  unE belongs to the operand that rides along as E; an E that is
+    // pass 1's own output carries none.  (Four bytes in what was padding: the argument block of the identity kernels keeps its layout.)
+    uint8_t     unA, unX, unE, unC;
     double      xi64;
     // complex data (HIP_C_32F / HIP_C_64F, ew_generic_cplx_kernel): imaginary parts of alpha / gamma (alpha64 / gamma64 hold the
     // real parts) and conjugation of the permuted operand A / of C
@@ -200,6 +205,11 @@ struct ReduceParams {
     // RED_GENERIC on real data with A's stride-1 mode among the REDUCED ones (round 6): one wave per kept element, lanes along that mode
     // (reduce_row_any_kernel) instead of one lane per kept element
     uint32_t    rowAny;
+    // Unary operators on real data (unary_op.h): D = alpha * reduce(unA(A)) + beta * unC(C).  unA is applied where A is loaded — not to
+    // the accumulators' identity element, not to split partials; unC once, where beta * C joins (the kernel's last step, or the finalize
+    // kernel when the range is split).
+    // (two bytes of the struct's tail padding: the argument block keeps its size)
+    uint8_t     unA, unC;
 };
 
 }  // namespace ctamd

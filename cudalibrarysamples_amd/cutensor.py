@@ -34,6 +34,8 @@ STATUS_SUCCESS, STATUS_NOT_INITIALIZED, STATUS_INVALID_VALUE = 0, 1, 7
 STATUS_NOT_SUPPORTED, STATUS_INSUFFICIENT_WORKSPACE, STATUS_IO_ERROR = 15, 19, 21
 OP_IDENTITY, OP_ADD, OP_MUL, OP_MAX, OP_MIN = 1, 3, 5, 6, 7
 OP_CONJ = 9
+# unary operators of an element-wise / reduction operand (real data; applied to the element before its scalar)
+OP_SQRT, OP_RELU, OP_RCP, OP_SIGMOID, OP_TANH, OP_EXP, OP_LOG, OP_ABS, OP_NEG = 2, 8, 10, 11, 12, 22, 23, 24, 25
 ALGO_DEFAULT, ALGO_DEFAULT_PATIENT = -1, -6
 WORKSPACE_MIN, WORKSPACE_DEFAULT, WORKSPACE_MAX = 1, 2, 3
 JIT_MODE_NONE = 0

@@ -119,6 +119,13 @@ class Plan:
 
 
 _OPS = {"ADD": ct.OP_ADD, "MUL": ct.OP_MUL, "MAX": ct.OP_MAX, "MIN": ct.OP_MIN}
+# per-operand unary operators (opA / opB / opC of the plan helpers below), by name or by cutensorOperator_t value
+_UNARY = {"IDENTITY": ct.OP_IDENTITY, "CONJ": ct.OP_CONJ, "SQRT": ct.OP_SQRT, "RELU": ct.OP_RELU, "RCP": ct.OP_RCP, "SIGMOID": ct.OP_SIGMOID,
+          "TANH": ct.OP_TANH, "EXP": ct.OP_EXP, "LOG": ct.OP_LOG, "ABS": ct.OP_ABS, "NEG": ct.OP_NEG}
+
+
+def _unary(op):
+    return _UNARY[op.upper()] if isinstance(op, str) else op
 
 
 def _desc3(handle, specs, dtype, alignment):
@@ -131,8 +138,8 @@ def contraction_plan(handle, extA, modesA, extB, modesB, extC, modesC, dtype=ct.
     dA, dB, dC = _desc3(handle, [(extA, strideA), (extB, strideB), (extC, strideC)], dtype, alignment)
     dD = tensor_descriptor(handle, extC, strideD, dtype, alignment) if strideD is not None else dC
     op = ctypes.c_void_p()
-    st = ct.cutensorCreateContraction(handle.h, ctypes.byref(op), dA, ct.i32(modesA), opA, dB, ct.i32(modesB),
-                                      opB, dC, ct.i32(modesC), opC, dD, ct.i32(modesC),
+    st = ct.cutensorCreateContraction(handle.h, ctypes.byref(op), dA, ct.i32(modesA), _unary(opA), dB, ct.i32(modesB),
+                                      _unary(opB), dC, ct.i32(modesC), _unary(opC), dD, ct.i32(modesC),
                                       ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
     for d in {id(x): x for x in (dA, dB, dC, dD)}.values():
         ct.cutensorDestroyTensorDescriptor(d)
@@ -144,8 +151,8 @@ def reduction_plan(handle, extA, modesA, extC, modesC, dtype=ct.R_32F, strideA=N
                    op_reduce=ct.OP_ADD, compute=None, alignment=128, opA=ct.OP_IDENTITY, opC=ct.OP_IDENTITY, **plan_kw):
     dA, dC = _desc3(handle, [(extA, strideA), (extC, strideC)], dtype, alignment)
     op = ctypes.c_void_p()
-    st = ct.cutensorCreateReduction(handle.h, ctypes.byref(op), dA, ct.i32(modesA), opA, dC, ct.i32(modesC),
-                                    opC, dC, ct.i32(modesC), op_reduce,
+    st = ct.cutensorCreateReduction(handle.h, ctypes.byref(op), dA, ct.i32(modesA), _unary(opA), dC, ct.i32(modesC),
+                                    _unary(opC), dC, ct.i32(modesC), op_reduce,
                                     ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
     ct.cutensorDestroyTensorDescriptor(dA)
     ct.cutensorDestroyTensorDescriptor(dC)
@@ -159,7 +166,7 @@ def permutation_plan(handle, extA, modesA, extB, modesB, dtype=ct.R_32F, strideA
     (elementwise_permute_padding.cu:178-195); the output buffer then holds extB + left + right per mode."""
     dA, dB = _desc3(handle, [(extA, strideA), (extB, strideB)], dtype, alignment)
     op = ctypes.c_void_p()
-    st = ct.cutensorCreatePermutation(handle.h, ctypes.byref(op), dA, ct.i32(modesA), opA, dB, ct.i32(modesB),
+    st = ct.cutensorCreatePermutation(handle.h, ctypes.byref(op), dA, ct.i32(modesA), _unary(opA), dB, ct.i32(modesB),
                                       ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
     ct.cutensorDestroyTensorDescriptor(dA)
     ct.cutensorDestroyTensorDescriptor(dB)
@@ -179,11 +186,12 @@ def permutation_plan(handle, extA, modesA, extB, modesB, dtype=ct.R_32F, strideA
 
 def binary_plan(handle, extA, modesA, extC, modesC, op="ADD", dtype=ct.R_32F, compute=None, alignment=128, opA=ct.OP_IDENTITY,
                 opC=ct.OP_IDENTITY, strideA=None, strideC=None, **plan_kw):
-    """D = op(alpha * perm(A), gamma * C) — cutensorCreateElementwiseBinary (elementwise_binary.cu:149-153)."""
+    """D = op(alpha * opA(perm(A)), gamma * opC(C)) — cutensorCreateElementwiseBinary (elementwise_binary.cu:149-153); opA / opC: a unary
+    operator by value or by name ("ABS", "RELU", ...)."""
     dA, dC = _desc3(handle, [(extA, strideA), (extC, strideC)], dtype, alignment)
     opd = ctypes.c_void_p()
-    st = ct.cutensorCreateElementwiseBinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), opA, dC, ct.i32(modesC),
-                                            opC, dC, ct.i32(modesC), _OPS[op],
+    st = ct.cutensorCreateElementwiseBinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), _unary(opA), dC, ct.i32(modesC),
+                                            _unary(opC), dC, ct.i32(modesC), _OPS[op],
                                             ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
     ct.cutensorDestroyTensorDescriptor(dA)
     ct.cutensorDestroyTensorDescriptor(dC)
@@ -193,13 +201,14 @@ def binary_plan(handle, extA, modesA, extC, modesC, op="ADD", dtype=ct.R_32F, co
 
 
 def trinary_plan(handle, extA, modesA, extB, modesB, extC, modesC, extD, modesD, opAB="ADD", opABC="ADD", dtype=ct.R_32F,
-                 compute=None, alignment=128, strideA=None, strideB=None, strideC=None, strideD=None, **plan_kw):
-    """D = opABC(opAB(alpha * perm(A), beta * perm(B)), gamma * perm(C)) — cutensorCreateElementwiseTrinary
+                 compute=None, alignment=128, strideA=None, strideB=None, strideC=None, strideD=None, opA=ct.OP_IDENTITY, opB=ct.OP_IDENTITY,
+                 opC=ct.OP_IDENTITY, **plan_kw):
+    """D = opABC(opAB(alpha * opA(perm(A)), beta * opB(perm(B))), gamma * opC(perm(C))) — cutensorCreateElementwiseTrinary
     (elementwise_trinary.cu:174-182)."""
     dA, dB, dC, dD = _desc3(handle, [(extA, strideA), (extB, strideB), (extC, strideC), (extD, strideD)], dtype, alignment)
     opd = ctypes.c_void_p()
-    st = ct.cutensorCreateElementwiseTrinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), ct.OP_IDENTITY, dB, ct.i32(modesB),
-                                             ct.OP_IDENTITY, dC, ct.i32(modesC), ct.OP_IDENTITY, dD, ct.i32(modesD),
+    st = ct.cutensorCreateElementwiseTrinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), _unary(opA), dB, ct.i32(modesB),
+                                             _unary(opB), dC, ct.i32(modesC), _unary(opC), dD, ct.i32(modesD),
                                              _OPS[opAB], _OPS[opABC], ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
     for d in (dA, dB, dC, dD):
         ct.cutensorDestroyTensorDescriptor(d)
