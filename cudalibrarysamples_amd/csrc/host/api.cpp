@@ -87,6 +87,9 @@ double num_elements(const cutensorTensorDescriptor& d) {
 std::string problem_key(const cutensorOperationDescriptor& op) {
     std::ostringstream ss;
     ss << (int)op.kind << ':' << (int)op.A.desc.dtype << ':' << (op.compute ? op.compute->id : -1);
+    // a converting element-wise problem (D's / C's type differs from A's) is another problem than the same-type one of the same shapes
+    if ((op.D.present && op.D.desc.dtype != op.A.desc.dtype) || (op.C.present && op.C.desc.dtype != op.A.desc.dtype))
+        ss << ":d" << (int)op.D.desc.dtype << ":c" << (op.C.present ? (int)op.C.desc.dtype : -1);
     auto put = [&](const TensorUse& u) {
         ss << '|';
         if (!u.present) return;
@@ -113,6 +116,7 @@ bool build_memo_key(const cutensorOperationDescriptor& op, const cutensorPlanPre
     k.operandsStreamed = (uint8_t)(pr.operandsStreamed != 0);
     k.kind = (uint8_t)op.kind; k.dtype = (uint8_t)op.A.desc.dtype; k.compute = (uint8_t)(op.compute ? op.compute->id : 255);
     k.scalarType = (uint8_t)op.scalarType;
+    k.dtypeD = op.D.present ? (uint8_t)op.D.desc.dtype : (uint8_t)255; k.dtypeC = op.C.present ? (uint8_t)op.C.desc.dtype : (uint8_t)255;
     k.op[0] = (uint8_t)op.A.op; k.op[1] = (uint8_t)op.B.op; k.op[2] = (uint8_t)op.C.op; k.op[3] = (uint8_t)op.opReduce;
     k.present = 0;
     uint32_t w = 0;
@@ -918,7 +922,7 @@ cutensorStatus_t cutensorCreatePermutation(const cutensorHandle_t handle, cutens
     std::string why;
     st = plan_elementwise(op, ep, &why);
     if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreatePermutation: %s", why.c_str()); return st; }
-    op.movedBytes = 2.0 * (double)dtype_size(op.D.desc.dtype) * num_elements(op.D.desc);   // elementwise_permute.cu:208
+    op.movedBytes = (double)(dtype_size(op.A.desc.dtype) + dtype_size(op.D.desc.dtype)) * num_elements(op.D.desc);   // elementwise_permute.cu:208
     return new_op(desc, op);
 } CTAMD_API_CATCH
 
@@ -944,7 +948,7 @@ cutensorStatus_t cutensorCreateElementwiseBinary(const cutensorHandle_t handle, 
     std::string why;
     st = plan_elementwise(op, ep, &why);
     if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateElementwiseBinary: %s", why.c_str()); return st; }
-    op.movedBytes = 3.0 * (double)dtype_size(op.D.desc.dtype) * num_elements(op.D.desc);
+    op.movedBytes = (double)(dtype_size(op.A.desc.dtype) + 2 * dtype_size(op.D.desc.dtype)) * num_elements(op.D.desc);
     return new_op(desc, op);
 } CTAMD_API_CATCH
 
@@ -1753,7 +1757,8 @@ static cutensorStatus_t build_padded_permutation(const PlanRequest& rq, cutensor
     cutensorOperationDescriptor inner = desc;
     inner.D.desc.stride = padded;
     // the interior starts `offset` elements into the buffer: keep the 16-byte-lane variants only if that is lane-aligned
-    const int64_t lane = 16 / (int64_t)dtype_size(desc.D.desc.dtype);
+    // (a converting permutation: the lane of the pair, 16 bytes of the narrower type)
+    const int64_t lane = 16 / (int64_t)std::min(dtype_size(desc.D.desc.dtype), dtype_size(desc.A.desc.dtype));
     if (offset % lane != 0) inner.D.desc.alignment = (uint32_t)dtype_size(desc.D.desc.dtype);
     const cutensorStatus_t st = plan_elementwise(inner, pl.ew, nullptr);
     if (st != CUTENSOR_STATUS_SUCCESS) return st;
@@ -2109,6 +2114,7 @@ static hipError_t run_elementwise(const EwPlan& ew, hipDataType dtype, double a,
     // the block kernel moves elements and scales them, nothing else: under a unary operator the plan runs on the kernel its tiles were
     // laid out for (same variant in the description, as for an attached operand)
     const int variant = (ew.variant == EW_BLOCK && p.unA != 0) ? ew.blockFrom : ew.variant;
+    if (ew.converts()) return launch_elementwise_convert(p, variant, (int)ew.dtypeA, (int)ew.dtypeD, stream);
     return launch_elementwise(p, variant, (int)dtype, stream);
 }
 
@@ -2155,8 +2161,9 @@ cutensorStatus_t cutensorPermute(const cutensorHandle_t handle, const cutensorPl
     hipError_t err = hipSuccess;
     void* out = B;
     if (plan->padFillElems != 0) {   // border (and interior, rewritten next) = padding value
-        err = launch_fill(B, plan->padFillElems, (int)plan->dtype, plan->padValue, stream);
-        out = static_cast<char*>(B) + plan->padOffsetElems * (int64_t)dtype_size(plan->dtype);
+        // (border and offset in the OUTPUT's type: plan->dtype is A's, which a converting permutation tells apart)
+        err = launch_fill(B, plan->padFillElems, (int)plan->ew.dtypeD, plan->padValue, stream);
+        out = static_cast<char*>(B) + plan->padOffsetElems * (int64_t)dtype_size(plan->ew.dtypeD);
     }
     if (err == hipSuccess) err = run_elementwise(plan->ew, plan->dtype, a, A, 0.0, nullptr, out, stream, nullptr, 0.0, scalar_imag(alpha, plan->scalarType));
     if (err != hipSuccess) { CT_LOG("cutensorPermute: %s", hipGetErrorString(err)); return CUTENSOR_STATUS_EXECUTION_FAILED; }
@@ -2428,6 +2435,9 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
         n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u,\"order\":%u}",
                           e.variant, e.p.E0, e.p.E1, e.p.rest.total, e.p.nBlocks, e.p.tile0, e.p.order);
         n = describe_unary(buf, len, n, e.p.unA, 0, e.p.unC);
+        // a converting plan (kernels/elementwise_convert.hip): the hipDataType values of A and of D
+        if (e.converts() && n > 1 && (size_t)n < len && buf[n - 1] == '}')
+            n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"convert\":[%d,%d]}", (int)e.dtypeA, (int)e.dtypeD);
     }
     return n;
 } CTAMD_API_CATCH_INT

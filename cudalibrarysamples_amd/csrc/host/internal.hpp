@@ -164,6 +164,9 @@ struct EwPlan {
     // variant EW_BLOCK: the variant the tile decomposition in p was laid out for (EW_GENERIC, or EW_TRANSPOSE when the block form was
     // preferred to mostly empty transposing tiles) — what runs when the block kernel cannot serve the launch (a unary operator on A)
     int        blockFrom = EW_GENERIC;
+    // data types of A and of D (and C): they differ in a converting plan, which runs on kernels/elementwise_convert.hip
+    hipDataType dtypeA = HIP_R_32F, dtypeD = HIP_R_32F;
+    bool converts() const { return dtypeA != dtypeD; }
 };
 // cutensorElementwiseTrinaryExecute: D = opABC(opAB(alpha A, beta B), gamma C) as one or two passes of the
 // element-wise kernels (plan_elementwise_trinary)
@@ -291,7 +294,7 @@ struct PlanMemoKey {
     uint8_t  kind = 0, dtype = 0, compute = 0, scalarType = 0;
     uint8_t  n[4] = {0, 0, 0, 0};
     uint8_t  op[4] = {0, 0, 0, 0};                 // opA, opB, opC, opReduce
-    uint8_t  present = 0, operandsStreamed = 0, pad_[2] = {0, 0};
+    uint8_t  present = 0, operandsStreamed = 0, dtypeD = 0, dtypeC = 0;   // (dtype above is A's; C's is 255 when there is no C)
     uint32_t used = 0;                             // int64 words of data[] in use
     uint32_t pad2_ = 0;                            // (no implicit padding anywhere in the head: it is hashed and compared bytewise)
     int64_t  data[3 * kMaxModes];                  // per tensor: modes, extents, strides

@@ -107,9 +107,25 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "MAX / MIN are not defined on complex data");
     if (dup_labels(A.modes) || dup_labels(D.modes) || (usesC && dup_labels(C.modes)))
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "repeated mode label inside one tensor");
-    if (A.desc.dtype != D.desc.dtype || (usesC && C.desc.dtype != D.desc.dtype))
-        return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types");
+    if (usesC && C.desc.dtype != D.desc.dtype) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: C's type differs from the output's");
+    // Type conversion (kernels/elementwise_convert.hip): cutensorPermute and the public binary form take an output (and C) of another type
+    // than A's — bf16 / fp16 <-> fp32 under CUTENSOR_COMPUTE_DESC_32F, fp32 <-> fp64 under CUTENSOR_COMPUTE_DESC_64F.  Never the
+    // trinary planner's passes (allowWide = false), never with a second permuted operand.
+    const bool conv = A.desc.dtype != D.desc.dtype;
+    if (conv) {
+        if (!allowWide || usesX || (op.kind != OpKind::Permutation && op.kind != OpKind::ElementwiseBinary))
+            return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types");
+        const hipDataType tA = A.desc.dtype, tD = D.desc.dtype;
+        auto h16t = [](hipDataType t) { return t == HIP_R_16BF || t == HIP_R_16F; };
+        int want = -1;                        // the pair's compute descriptor (index of the exported constants)
+        if ((h16t(tA) && tD == HIP_R_32F) || (tA == HIP_R_32F && h16t(tD))) want = 4;                              // 32F
+        else if ((tA == HIP_R_32F && tD == HIP_R_64F) || (tA == HIP_R_64F && tD == HIP_R_32F)) want = 5;           // 64F
+        if (want < 0) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: no conversion between this pair of types");
+        if (op.compute == nullptr || op.compute->id != want)
+            return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: the pair needs its own compute descriptor (32F for 16 <-> 32 bits, 64F for 32 <-> 64)");
+    }
     // unary operators: IDENTITY, CONJ (a no-op on real data), and on real data the nine of kernels/unary_op.h
+    if (const char* r = unary_refusal(A.op, A.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     if (const char* r = unary_refusal(A.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     if (usesC) if (const char* r = unary_refusal(C.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     if (usesX) {
@@ -208,6 +224,49 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     }
     if (!fill_rest(p.rest, rest)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "too many unfusable modes");
     for (size_t i = 0; i < rest.size(); ++i) p.restX[i] = rest[i].sX;
+
+    plan.dtypeA = A.desc.dtype;
+    plan.dtypeD = D.desc.dtype;
+    if (conv) {
+        // ---- variant of a converting plan (kernels/elementwise_convert.hip) ----------------------
+        // a lane holds LV = 16 / min(sizeof A, sizeof D) elements: one 16-byte access on the narrow side, two on the wide side
+        const int64_t szA = (int64_t)dtype_size(A.desc.dtype), szD = (int64_t)dtype_size(D.desc.dtype);
+        const int64_t lv = 16 / std::min(szA, szD);
+        auto multLv = [lv](int64_t s) { return s % lv == 0; };
+        const bool aligned = (A.desc.alignment % 16 == 0) && (D.desc.alignment % 16 == 0) && (!usesC || C.desc.alignment % 16 == 0);
+        bool restOK = true;
+        for (const EwMode& m : rest) restOK = restOK && multLv(m.sA) && multLv(m.sD) && (!usesC || multLv(m.sC));
+        const bool cOK = !usesC || p.sC0 != 1 || multLv(p.sC1);      // (C: 16-byte lanes along dim0, or element by element)
+        plan.variant = EW_GENERIC;
+        int t0 = 64, t1 = 4;
+        if (aligned && restOK && cOK && p.sD0 == 1 && p.E0 % lv == 0) {
+            if (i1 >= 0 && p.sA1 == 1 && p.sA0 != 1 && p.E1 % lv == 0 && multLv(p.sA0) && multLv(p.sD1)) {
+                // T0 x 64 tiles; the LDS tile holds the narrower type — A's when the plan narrows AND reads a C term (one rounding, after
+                // the combiner) — within 32 KiB: the widest of 256 / 128 / 64 the extent fills, as the fp32 kernel's rule
+                plan.variant = EW_TRANSPOSE; t0 = 64; t1 = 64;
+                const int64_t park = (szD < szA && !usesC) ? szD : szA;
+                for (int64_t cand = std::min<int64_t>(256, 32768 / (64 * park)); cand > 64; cand /= 2)
+                    if (p.E0 % cand == 0 || p.E0 >= 4 * cand) { t0 = (int)cand; break; }
+            } else if (p.sA0 == 1 && multLv(p.sA1) && multLv(p.sD1)) {
+                plan.variant = EW_ROWCOPY; t0 = 64 * (int)lv; t1 = 8;
+            }
+        }
+        p.tile0 = (uint32_t)t0;
+        p.tile1 = (uint32_t)t1;
+        p.tiles0 = (p.E0 + t0 - 1) / t0;
+        p.tiles1 = (p.E1 + t1 - 1) / t1;
+        p.divTiles0 = make_fastdiv(p.tiles0);
+        p.divTiles1 = make_fastdiv(p.tiles1);
+        const uint64_t nb = (uint64_t)p.tiles0 * p.tiles1 * p.rest.total;
+        if (nb >= (1ull << 31)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "tensor too large for the tile index space");
+        p.nBlocks = (uint32_t)nb;
+        // the per-XCD tile order under the same pitch rule as the same-type kernels: rows >= 1 MiB apart on both sides, each in its own type
+        p.order = 0;
+        p.idsPerXcd = (uint32_t)((nb + 7) / 8);
+        p.divRest = make_fastdiv(p.rest.total);
+        if (plan.variant == EW_TRANSPOSE && p.rest.total >= 64 && nb >= 4096 && p.sA0 * szA >= (1 << 20) && p.sD1 * szD >= (1 << 20)) p.order = 1;
+        return CUTENSOR_STATUS_SUCCESS;
+    }
 
     // ---- variant --------------------------------------------------------------------------
     // vector paths: fp32 (4-element lanes) and bf16 / fp16 (8-element lanes); "mult4" = multiple of the lane width

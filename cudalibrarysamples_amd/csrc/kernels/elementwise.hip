@@ -21,6 +21,10 @@
 //   EW_GENERIC    anything else (odd extents, unaligned bases, 2- and 8-byte types): one element
 //                 per lane, lanes along dim0.
 //
+// A and D (and C) have ONE data type here; the kernels that read one element width and write another (cutensorPermute and the binary
+// form with an output of another type: ew_rowcopy_convert_kernel, ew_transpose_convert_kernel, ew_generic_convert_kernel) are
+// elementwise_convert.hip, and the device helpers both files use are elementwise_common.h.
+//
 // The kernels of real data are in elementwise_kernels.inc, which this file includes twice: as x_kernel (the identity twins) and as
 // x_un_kernel (the twins that apply the operands' unary operators, unary_op.h).  The sections below keep each family's constants and
 // device helpers; the launchers at the end pick variant, type and twin.
@@ -30,6 +34,7 @@
 #include <stdint.h>
 #include <cstring>
 
+#include "elementwise_common.h"
 #include "launch.h"
 #include "params.h"
 #include "unary_op.h"
@@ -39,35 +44,6 @@ namespace ctamd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint32_t ew_fast_div(uint32_t n, const FastDiv& d) {
-    return (d.d < 2) ? n : (__umulhi(n, d.magic) >> d.shift);
-}
-
-// offsets of a rest index in A (slot 0), D (slot 1) and C (slot 2)
-__device__ __forceinline__ void rest_offsets(const ModeGroup& g, uint32_t idx, int64_t& oA, int64_t& oD,
-                                             int64_t& oC) {
-    oA = oD = oC = 0;
-#pragma unroll
-    for (int i = 0; i < kMaxGroupModes; ++i) {   // padding modes: {d = 1, magic = 0, stride = 0}
-        const uint32_t q = __umulhi(idx, g.div[i].magic) >> g.div[i].shift;
-        const uint32_t digit = idx - q * g.div[i].d;
-        oA += (int64_t)digit * g.stride[0][i];
-        oD += (int64_t)digit * g.stride[1][i];
-        oC += (int64_t)digit * g.stride[2][i];
-        idx = q;
-    }
-}
-
-// binary combiners of the element-wise family (cutensorOperator_t values; 0 = ADD)
-template <typename S>
-__device__ __forceinline__ S ew_comb(int op, S x, S y) {
-    switch (op) {
-        case 5: return x * y;                 // CUTENSOR_OP_MUL
-        case 6: return x > y ? x : y;         // CUTENSOR_OP_MAX
-        case 7: return x < y ? x : y;         // CUTENSOR_OP_MIN
-        default: return x + y;                // CUTENSOR_OP_ADD
-    }
-}
 __device__ __forceinline__ f32x4 ew_comb4(int op, f32x4 x, f32x4 y) {
     f32x4 r;
 #pragma unroll
@@ -85,36 +61,6 @@ __device__ __forceinline__ int64_t rest_offset_x(const ModeGroup& g, const int64
         idx = q;
     }
     return o;
-}
-
-struct TileId { uint32_t t0, t1, rest; };
-__device__ __forceinline__ TileId decode_tile(const Ew2DParams& p, uint32_t b) {
-    TileId t;
-    uint32_t q = ew_fast_div(b, p.divTiles0);
-    t.t0 = b - q * p.tiles0;
-    const uint32_t q2 = ew_fast_div(q, p.divTiles1);
-    t.t1 = q - q2 * p.tiles1;
-    t.rest = q2;
-    return t;
-}
-
-// Tile of workgroup-loop index b under the planner's tile order (Ew2DParams::order); false = this index names no tile.
-//   order 0: ids walk dim0 tiles, dim1 tiles, rest.
-//   order 1 (both the rows A is read by and the rows D is written by lie a large pitch apart, e.g. the full reversal
-//   A[a,b,c] -> C[c,b,a] at 2048^3, 16 MiB on both sides): ids walk rest, then dim1, then dim0, and XCD x = workgroup id % 8
-//   takes the x-th eighth of that sequence, so that at any time one XCD works inside a few dim0 / dim1 tiles — a few hundred
-//   distinct pages per XCD instead of every page of both tensors (fp32: 5.79 -> 6.31 TB/s, profiles/r03_transpose_sweep3_rev.jsonl;
-//   the same order WITHOUT the per-XCD split is the worst: 4.14)
-__device__ __forceinline__ bool ordered_tile(const Ew2DParams& p, uint32_t b, TileId& t) {
-    if (p.order == 0) { t = decode_tile(p, b); return true; }
-    const uint32_t id = (b & 7u) * p.idsPerXcd + (b >> 3);
-    if (id >= p.nBlocks) return false;
-    const uint32_t q = ew_fast_div(id, p.divRest);
-    t.rest = id - q * p.rest.total;
-    const uint32_t q2 = ew_fast_div(q, p.divTiles1);
-    t.t1 = q - q2 * p.tiles1;
-    t.t0 = q2;
-    return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -138,22 +84,6 @@ constexpr int RC_T0 = 256, RC_T1 = 8;
 //                drained with 2-byte LDS accesses (16 + 16 per lane and tile — a few hundred LDS cycles against
 //                ~2 k cycles of HBM time for the tile's 16 KiB), HBM sees 128-byte segments on both sides
 // ---------------------------------------------------------------------------------------------
-typedef uint32_t u32x4e __attribute__((ext_vector_type(4)));
-
-template <bool BF> __device__ __forceinline__ float h16_to_f32(uint16_t v) {
-    if constexpr (BF) return __uint_as_float((uint32_t)v << 16);
-    else return (float)__builtin_bit_cast(_Float16, v);
-}
-template <bool BF> __device__ __forceinline__ uint16_t f32_to_h16(float f) {
-    if constexpr (BF) {
-        uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    } else {
-        return __builtin_bit_cast(uint16_t, (_Float16)f);
-    }
-}
 template <bool BF> __device__ __forceinline__ void h16_unpack(u32x4e v, float (&f)[8]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) { f[2 * i] = h16_to_f32<BF>((uint16_t)(v[i] & 0xffffu)); f[2 * i + 1] = h16_to_f32<BF>((uint16_t)(v[i] >> 16)); }

@@ -99,6 +99,9 @@ enum EwVariant : int {
                        // through LDS, permuted inside (Ew2DParams::blk*); falls back to EW_GENERIC when a C / E / X operand is attached
 };
 hipError_t launch_elementwise(const Ew2DParams& p, int variant, int dtype, hipStream_t stream);
+// the converting kernels (elementwise_convert.hip): A of dtypeA, D and C of dtypeD — bf16 / fp16 <-> fp32 and fp32 <-> fp64; variants
+// EW_TRANSPOSE / EW_ROWCOPY / EW_GENERIC with a lane of 16 / min(sizeof A, sizeof D) elements; any other pair or variant is an error
+hipError_t launch_elementwise_convert(const Ew2DParams& p, int variant, int dtypeA, int dtypeD, hipStream_t stream);
 // D[0 .. n) = value (contiguous; the padded-permutation border fill)
 hipError_t launch_fill(void* D, uint64_t n, int dtype, double value, hipStream_t stream);
 

@@ -132,6 +132,27 @@ def _desc3(handle, specs, dtype, alignment):
     return [tensor_descriptor(handle, e, s, dtype, alignment) for (e, s) in specs]
 
 
+def _pair_compute(dtype, dtype_out):
+    """the compute descriptor of an element-wise plan whose output type may differ from A's (type conversion: bf16 / fp16 <-> fp32 under
+    32F, fp32 <-> fp64 under 64F; the library refuses every other pair)"""
+    if dtype_out == dtype:
+        return _DTYPE_COMPUTE[dtype]
+    return "64F" if ct.R_64F in (dtype, dtype_out) else "32F"
+
+
+def _typed_value(value, dtype):
+    """one real value in the storage format of dtype (CUTENSOR_OPERATION_DESCRIPTOR_PADDING_VALUE is read in the output's type)"""
+    import struct
+    if dtype == ct.R_64F:
+        return ctypes.c_double(value)
+    if dtype == ct.R_16F:
+        return ctypes.c_uint16(struct.unpack("<H", struct.pack("<e", value))[0])
+    if dtype == ct.R_16BF:
+        u = struct.unpack("<I", struct.pack("<f", value))[0]
+        return ctypes.c_uint16(((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF)      # to nearest even
+    return ctypes.c_float(value)
+
+
 def contraction_plan(handle, extA, modesA, extB, modesB, extC, modesC, dtype=ct.R_32F, strideA=None,
                      strideB=None, strideC=None, strideD=None, compute=None, alignment=128, opA=ct.OP_IDENTITY,
                      opB=ct.OP_IDENTITY, opC=ct.OP_IDENTITY, **plan_kw):
@@ -161,13 +182,16 @@ def reduction_plan(handle, extA, modesA, extC, modesC, dtype=ct.R_32F, strideA=N
 
 
 def permutation_plan(handle, extA, modesA, extB, modesB, dtype=ct.R_32F, strideA=None, strideB=None,
-                     compute=None, alignment=128, padding=None, opA=ct.OP_IDENTITY, **plan_kw):
+                     compute=None, alignment=128, padding=None, opA=ct.OP_IDENTITY, dtypeB=None, **plan_kw):
     """padding = (left[], right[], value): CUTENSOR_OPERATION_DESCRIPTOR_PADDING_* per output mode
-    (elementwise_permute_padding.cu:178-195); the output buffer then holds extB + left + right per mode."""
-    dA, dB = _desc3(handle, [(extA, strideA), (extB, strideB)], dtype, alignment)
+    (elementwise_permute_padding.cu:178-195); the output buffer then holds extB + left + right per mode.
+    dtypeB: the output's data type where it differs from A's (dtype) — a converting permutation; None: the same type."""
+    dtypeB = dtype if dtypeB is None else dtypeB
+    dA = tensor_descriptor(handle, extA, strideA, dtype, alignment)
+    dB = tensor_descriptor(handle, extB, strideB, dtypeB, alignment)
     op = ctypes.c_void_p()
     st = ct.cutensorCreatePermutation(handle.h, ctypes.byref(op), dA, ct.i32(modesA), _unary(opA), dB, ct.i32(modesB),
-                                      ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
+                                      ct.compute_desc(compute or _pair_compute(dtype, dtypeB)))
     ct.cutensorDestroyTensorDescriptor(dA)
     ct.cutensorDestroyTensorDescriptor(dB)
     ct.check(st)
@@ -178,21 +202,24 @@ def permutation_plan(handle, extA, modesA, extB, modesB, dtype=ct.R_32F, strideA
         r = (ctypes.c_int32 * n)(*right)
         ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 4, l, 4 * n))    # PADDING_LEFT
         ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 5, r, 4 * n))    # PADDING_RIGHT
-        v = ctypes.c_double(value) if dtype == ct.R_64F else ctypes.c_float(value)
+        v = _typed_value(value, dtypeB) if dtypeB != dtype else (ctypes.c_double(value) if dtype == ct.R_64F else ctypes.c_float(value))
         ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 6, ctypes.byref(v), ctypes.sizeof(v)))   # PADDING_VALUE
     plan_kw.setdefault("workspace_limit", 0)   # elementwise_permute.cu:183-187
     return Plan(handle, op, "permutation", dtype, **plan_kw)
 
 
 def binary_plan(handle, extA, modesA, extC, modesC, op="ADD", dtype=ct.R_32F, compute=None, alignment=128, opA=ct.OP_IDENTITY,
-                opC=ct.OP_IDENTITY, strideA=None, strideC=None, **plan_kw):
+                opC=ct.OP_IDENTITY, strideA=None, strideC=None, dtypeC=None, **plan_kw):
     """D = op(alpha * opA(perm(A)), gamma * opC(C)) — cutensorCreateElementwiseBinary (elementwise_binary.cu:149-153); opA / opC: a unary
-    operator by value or by name ("ABS", "RELU", ...)."""
-    dA, dC = _desc3(handle, [(extA, strideA), (extC, strideC)], dtype, alignment)
+    operator by value or by name ("ABS", "RELU", ...).  dtypeC: the data type of C and D where it differs from A's (dtype) — a
+    converting plan; None: the same type."""
+    dtypeC = dtype if dtypeC is None else dtypeC
+    dA = tensor_descriptor(handle, extA, strideA, dtype, alignment)
+    dC = tensor_descriptor(handle, extC, strideC, dtypeC, alignment)
     opd = ctypes.c_void_p()
     st = ct.cutensorCreateElementwiseBinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), _unary(opA), dC, ct.i32(modesC),
                                             _unary(opC), dC, ct.i32(modesC), _OPS[op],
-                                            ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
+                                            ct.compute_desc(compute or _pair_compute(dtype, dtypeC)))
     ct.cutensorDestroyTensorDescriptor(dA)
     ct.cutensorDestroyTensorDescriptor(dC)
     ct.check(st)
