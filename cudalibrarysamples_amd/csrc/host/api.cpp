@@ -156,9 +156,9 @@ namespace {
 
 // any experiment knob that changes what cutensorCreatePlan decides: the memo stands aside while one is set
 bool plan_env_override() {
-    return ctamd_research_env("CUTENSOR_AMD_FORCE") || ctamd_research_env("CUTENSOR_AMD_XCD_BALANCE") || CTAMD_HOOK_ENV("CUTENSOR_AMD_FUSED_FOLD") ||
-           ctamd_research_env("CUTENSOR_AMD_H16_TRANSPOSE_T1") || CTAMD_HOOK_ENV("CUTENSOR_AMD_NT") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") || ctamd_research_env("CUTENSOR_AMD_H16_SPLITK") ||
-           ctamd_research_env("CUTENSOR_AMD_KORDER") || ctamd_research_env("CUTENSOR_AMD_ABLATION") || CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") || CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") ||
+    return CTAMD_HOOK_ENV("CUTENSOR_AMD_FORCE") || CTAMD_HOOK_ENV("CUTENSOR_AMD_XCD_BALANCE") || CTAMD_HOOK_ENV("CUTENSOR_AMD_FUSED_FOLD") ||
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_TRANSPOSE_T1") || CTAMD_HOOK_ENV("CUTENSOR_AMD_NT") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_SPLITK") ||
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER") || CTAMD_HOOK_ENV("CUTENSOR_AMD_ABLATION") || CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") || CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X");
 }
 
@@ -1552,7 +1552,7 @@ static TiledRoute rank_tiled_candidates(const PlanRequest& rq, const cutensorPla
     if (r.mfmaPath) r.ch = rank_contraction_choices(v, rq.wsLimit, numCUs, rq.pr.operandsStreamed != 0);
     else if (r.h16Path && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", 'f'))   // "force" (measurement): the general family also where the aligned 16-bit kernels apply
         r.ch = rank_h16_choices(v, rq.wsLimit, numCUs);
-    if (r.mfmaPath && desc.scalarType == HIP_R_32F && !names_candidate(rq.pr) && !ctamd_research_env("CUTENSOR_AMD_KORDER"))
+    if (r.mfmaPath && desc.scalarType == HIP_R_32F && !names_candidate(rq.pr) && !CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER"))
         r.tDirectUs = f32_direct_estimate_us(v, r.ch);
     if (r.mfmaPath) {
         // a reduced-precision compute descriptor: the bf16 / fp16-rate kernels when the model (or CUTENSOR_AMD_F32X=force) says so.
@@ -1647,7 +1647,7 @@ static size_t select_candidate(const PlanRequest& rq, cutensorPlan& pl, const st
     if ((int)pr.algo >= 0) idx = std::min<size_t>((size_t)pr.algo, ch.size() - 1);
     else if (pr.kernelRank > 0) idx = std::min<size_t>((size_t)pr.kernelRank, ch.size() - 1);
     else if (patient) idx = (size_t)autotune_contraction(handle, rq.desc, pl.view, ch);
-    if (const char* f = ctamd_research_env("CUTENSOR_AMD_FORCE")) {   // "kernel:splitK" experiment knob
+    if (const char* f = CTAMD_HOOK_ENV("CUTENSOR_AMD_FORCE")) {   // "kernel:splitK" experiment knob
         int fk = -1; unsigned fs = 1;
         if (std::sscanf(f, "%d:%u", &fk, &fs) >= 1)
             for (size_t i = 0; i < ch.size(); ++i)
@@ -1672,7 +1672,7 @@ static void tune_f32_splitk(const PlanRequest& rq, cutensorPlan& pl) {
     // differ by +-1.5 %, below the 1-tile-in-32 (3 %) granularity of the headline split, so the apportionment comes out uniform
     // 
     if (pick.splitK >= 64 && pl.view.totL == 1 && pl.gett.tilesM * pl.gett.tilesN == 1) {
-        const char* env = ctamd_research_env("CUTENSOR_AMD_XCD_BALANCE");
+        const char* env = CTAMD_HOOK_ENV("CUTENSOR_AMD_XCD_BALANCE");
         if (env && env[0] == '1') pl.gett.xcdTiles = calibrate_xcd_split(rq.handle, rq.desc, pl);
     }
     // In-launch fold of the split-K partials: only when every workgroup of the launch owns a CU of its own (they wait for each other)
@@ -2495,16 +2495,7 @@ int ctamdProfileEnd(cutensorHandle_t handle, float* meanMs, float* minMs) try {
 
 // Instantiated fp32 GETT kernels (test coverage bookkeeping): table size, and whether entry i is a
 // measurement-only ablation variant (never planned unless CUTENSOR_AMD_ABLATION is set).
-// 1 when the library was built with RESEARCH=1 (retired kernel families, TIMED / XST / EP instantiations, measurement switches)
-int ctamdResearchKernelsBuilt(void) try {
-#if defined(CTAMD_RESEARCH_KERNELS)
-    return 1;
-#else
-    return 0;
-#endif
-} CTAMD_API_CATCH_INT
-
-// 1 when this library reads the test / measurement switches (CTAMD_HOOK_ENV: the lib_hooks/ flavour and research builds)
+// 1 when this library reads the test / measurement switches (CTAMD_HOOK_ENV: the lib_hooks/ flavour)
 int ctamdTestHooksBuilt(void) try { return CTAMD_HOOKS_BUILT; } CTAMD_API_CATCH_INT
 
 int ctamdKernelCount(void) try {

@@ -174,7 +174,7 @@ cutensorStatus_t build_contraction_view(const cutensorOperationDescriptor& op, C
     // explicit digit list, fastest first, e.g. "d,c:4,b,c" = mode d, the inner 4 of mode c, mode b, the
     // rest of c (labels as characters).  Any order of the contracted digits is a valid GETT view; the
     // order decides how a K slice maps to memory in A and B.
-    const char* korder = ctamd_research_env("CUTENSOR_AMD_KORDER");
+    const char* korder = CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER");
     bool followB = (!kContigA && kContigB);
     bool custom = false;
     if (korder && korder[0] == 'B' && korder[1] == 0) followB = true;
@@ -349,7 +349,7 @@ std::vector<ContractionChoice> rank_contraction_choices(const ContractionView& v
     const double hbm = 6.0e12, l2bw = 20.0e12;
     const double M = (double)v.totM, N = (double)v.totN, K = (double)v.totK, L = (double)v.totL;
 
-    const bool withAblations = ctamd_research_env("CUTENSOR_AMD_ABLATION") != nullptr;
+    const bool withAblations = CTAMD_HOOK_ENV("CUTENSOR_AMD_ABLATION") != nullptr;
     // byte span of an operand beyond its batch offset: the streaming kernels address it through a buffer
     // descriptor with 32-bit byte offsets
     auto span_bytes = [&](bool slotA) {
@@ -534,7 +534,7 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     if (sweep && h16_sweep_fill(v) < 0.45 && !CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES")) return false;
     const bool ragged = h16_needs_rag(v);         // the candidates are the kernels that have a RAG instantiation
     // The 16-bit kernels address an operand with 32-bit byte offsets relative to a 64-bit base that moves with the workgroup
-    // tile, the wave and the K-tile (gett_h16.hip, HOperand / HOdometer): what has to stay below 2^31 bytes is the span of
+    // tile, the wave and the K-tile (gett_h16_common.h HOperand, gett_h16x_common.h VOdometer): what has to stay below 2^31 bytes is the span of
     // ONE 256-row x 64-k tile, whatever the size of the tensor.
     auto tile_span_bytes = [&](bool slotA) {
         uint64_t n = 1;
@@ -637,7 +637,7 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         const double ts = stripsOK ? strip_us(cand, mi, ni) : 1e30;
         if (ts < 0.97 * best) { best = ts; var = cand; split = 1; c.stripKernel = h16_entry(H16_W4Q, layoutIdx); c.mInt = mi; c.nInt = ni; }
     };
-    const bool usable = forced && layoutIdx + var < count && tab[layoutIdx + var].ablation != 2;   // a retired family asked for in a production build: ignored
+    const bool usable = forced && layoutIdx + var < count && tab[layoutIdx + var].ablation != 2;   // a retired family asked for: ignored
     if (ragged && forced) {
         // CUTENSOR_AMD_H16_WAVES names the kernel: one of those that mask a partial K-tile (4x, 4m, 4m4, 4q), or the general family
         if (!usable || (var != H16_W4X && var != H16_W4M && var != H16_W4M4 && var != H16_W4Q)) return false;
@@ -649,7 +649,7 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     } else if (forced && usable) {
         split = auto_split(var);
     } else {
-        // the planner's own choice: the 256 x 256 family (four-wave 16x16x32 kernel; eight-wave kernel for short K ranges, below), the
+        // the planner's own choice: the 256 x 256 family (four-wave 16x16x32 kernel, one-tile and persistent), the
         // 128 x 128 mid-size family and the 64 x 64 tile, each without split-K and at its automatic split
         static const bool noPersistent = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16P"); return e && e[0] == '0'; }();
         // The persistent kernel earns its place by streaming interior tiles into each other, which needs the epilogue that stays out of the
@@ -667,7 +667,7 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
             if (cand != H16_W4P || (!noPersistent && streamable)) consider(cand);
     }
     c.kernel = layoutIdx + var;
-    if (const char* fs = ctamd_research_env("CUTENSOR_AMD_H16_SPLITK")) {   // measurement knob: this many slices (if the workspace allows)
+    if (const char* fs = CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_SPLITK")) {   // measurement knob: this many slices (if the workspace allows)
         const uint64_t want = std::strtoull(fs, nullptr, 10);
         if (want >= 1 && want <= kTiles && want * perSliceBytes <= std::max<uint64_t>(wsLimit, 1)) split = want;
         if (want == 1) split = 1;
@@ -695,7 +695,7 @@ std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64
     const int variant = tab[base.kernel].variant, layoutIdx = base.kernel - variant;
     for (int other : {H16_W8, H16_W4X, H16_W4P, H16_W4M, H16_W4M4, H16_W8M, H16_W4Q, H16_W4V, H16_W4R, H16_S, H16_W4S, H16_W4}) {
         if (other == variant || layoutIdx + other >= count) continue;
-        if (tab[layoutIdx + other].ablation == 2) continue;        // a retired family, not built into this library (research builds only)
+        if (tab[layoutIdx + other].ablation == 2) continue;        // the slot of a retired family: no kernel behind it
         ContractionChoice c = base;
         c.kernel = layoutIdx + other;
         c.stripKernel = -1;                                        // the whole grid on this kernel

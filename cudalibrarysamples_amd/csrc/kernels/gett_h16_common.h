@@ -1,5 +1,13 @@
-// gett_h16_common.h — shared pieces of the 16-bit GETT kernels (gett_h16.hip, gett_h16v.hip): types, the LDS-DMA / fragment-read
-// primitives, the operand staging tables (HOperand), the K odometer and the epilogue.  See gett_h16.hip for the LDS image.
+// gett_h16_common.h — shared pieces of the 16-bit GETT kernels (gett_h16v.hip, gett_h16p.hip; gett_h16.hip holds their table): types, the
+// operand staging tables (HOperand), the epilogue and the table slot of a retired family.  The LDS-DMA / fragment-read primitives and the K
+// odometer are in gett_h16x_common.h.
+//
+// LDS image of an operand's K-tile (64 k): half-tiles of 128 rows = 16 KiB, staged by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per
+// wave-instruction).  Which 16-byte unit of the half-tile a lane fetches is free, so the image is shaped by permuting the *source* units:
+//   - K-contiguous operand (LAY_K): image [128 rows][64 k] (128-byte rows); unit p of row r holds k-unit p ^ ((r >> 1) & 7): the
+//     ds_read_b128 fragment reads are conflict-free;
+//   - free-contiguous operand (LAY_F): image [64 k][128 rows] (256-byte k-rows); unit p of k-row k holds row-unit
+//     p ^ 4 (k & 3) ^ 2 ((k >> 3) & 1); fragments are read with the transposing ds_read_b64_tr_b16 (x_offF, gett_h16x_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,19 +40,10 @@ __device__ __forceinline__ uint64_t h_uniform64(uint64_t v) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
     return ((uint64_t)hi << 32) | lo;
 }
-// descriptor whose base is the (wave-uniform) byte address `addr`
-__device__ __forceinline__ HRsrc h_make_rsrc(uint64_t addr) {
-    HRsrc r;
-    r[0] = (int)(uint32_t)addr;
-    r[1] = (int)((uint32_t)(addr >> 32) & 0xffffu);
-    r[2] = -1;
-    r[3] = 0x00020000;
-    return r;
-}
 // Minimum over the 64 lanes of a wave (all active) of byte offsets that lie within 2^31 of each other (the planner admits the
 // 16-bit kernels only when ONE tile spans less than 2^31 bytes): the 32-bit differences to the first lane's value are reduced with
 // four DPP steps inside each row of 16 lanes and four v_readlane — ~50 cycles.  (As six __shfl_xor rounds on 64-bit values this was
-// 24 dependent ds_bpermute per kernel start, ~2.5k cycles of every workgroup's prologue: tools/h16_small_timeline.py.)
+// 24 dependent ds_bpermute per kernel start, ~2.5k cycles of every workgroup's prologue: in-kernel stamps)
 __device__ __forceinline__ int64_t h_wave_min(int64_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int64_t ref = (int64_t)h_uniform64((uint64_t)v);
@@ -60,23 +59,6 @@ __device__ __forceinline__ int64_t h_wave_min(int64_t v) {
     return ref + (int64_t)(m01 < m23 ? m01 : m23);
 #else
     return v;
-#endif
-}
-
-// 64 lanes x 16 B -> the 1-KiB LDS piece at byte address ldsByte (wave-uniform).  Hidden from the
-// compiler's wait-count bookkeeping on purpose: completion is counted by hand (CTAMD_H_VMCNT).
-// s_nop 4: the SGPR operands may come straight from a v_readfirstlane (VALU-write -> VMEM-read hazard).
-template <bool PAD = true>
-__device__ __forceinline__ void h_dma16(HRsrc rsrc, uint32_t laneBytes, uint32_t ldsByte) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (PAD)
-        asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                     :: "s"(ldsByte), "v"(laneBytes), "s"(rsrc) : "memory");
-    else   // main loop: every SGPR operand was produced by the scalar ALU, or long ago
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                     :: "s"(ldsByte), "v"(laneBytes), "s"(rsrc) : "memory");
-#else
-    (void)rsrc; (void)laneBytes; (void)ldsByte;
 #endif
 }
 
@@ -228,63 +210,6 @@ struct HEpilogue {
         return v;
     }
 
-    // park fragment F (0..3) of the current pass: element (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31) = acc[r]
-    __device__ __forceinline__ void park(int F, const f32x16& acc, int lane) const {
-        float* st = scratch + F * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = alpha * acc[r];
-    }
-
-    // ---- 64-column form (the default kernel: a wave's two B-side fragments are adjacent columns) --------------------------
-    // Staging image [16 rows][64 columns] fp32 = 4 KiB per wave at `scratch`: half HALF (rows 16 HALF + [0,16)) of the fragment
-    // pair (c0: columns 0-31, c1: columns 32-63).  One store instruction then writes 8 rows x 128 contiguous bytes (whole cache
-    // lines; tools/ubench/store_pattern.hip: 128 MiB of such stores drain in 25.8 us against 34.2 us for 64-byte row pieces).
-    template <int HALF>
-    __device__ __forceinline__ void park_pair(const f32x16& c0, const f32x16& c1, int lane) const {
-        float* st = scratch + ((lane >> 5) * 4) * 64 + (lane & 31);
-#pragma unroll
-        for (int r = 8 * HALF; r < 8 * HALF + 8; ++r) {
-            const int row = (r & 3) + 8 * ((r >> 2) & 1);
-            st[row * 64]      = alpha * c0[r];
-            st[row * 64 + 32] = alpha * c1[r];
-        }
-    }
-    // rows mB + [0,16), columns nB + [0,64)
-    template <bool BF, int ST = 0>
-    __device__ __forceinline__ void flush_pair(const GettParams& p, uint32_t mB, uint32_t nB, int lane) const {
-        if (vecD && (beta == 0.f || vecC)) {
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int cidx = lane + 64 * it, row = cidx >> 3, piece = cidx & 7;
-                const float* src = scratch + row * 64 + piece * 8;
-                f32x4 v0 = *reinterpret_cast<const f32x4*>(src);
-                f32x4 v1 = *reinterpret_cast<const f32x4*>(src + 4);
-                const uint32_t m = mB + row, n = nB + 8 * piece;
-                if (m < Mtot && n < Ntot) {
-                    int64_t offD, offC;
-                    offsets(p, m, n, offD, offC);
-                    s16x8 out;
-                    if (beta != 0.f) out = h_round8_with_c<BF>(v0, v1, beta, load16(C + offC, n));
-                    else out = h_round8<BF>(v0, v1);
-                    if constexpr (ST == 0) store16(D + offD, out, n);   // nontemporal: not read again by this kernel; keeps the operand panels in L2
-                    else if constexpr (ST == 1) *(HGlbS8)(uintptr_t)(D + offD) = out;
-                    else asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(D + offD), "v"(out) : "memory");
-                }
-            }
-            return;
-        }
-#pragma unroll 1
-        for (int row = 0; row < 16; ++row) {           // element-wise form (any strides): lane = column
-            const uint32_t m = mB + row, n = nB + lane;
-            if (m < Mtot && n < Ntot) {
-                int64_t offD, offC;
-                offsets(p, m, n, offD, offC);
-                float val = scratch[row * 64 + lane];
-                *(HGlbU16)(uintptr_t)(D + offD) = (beta != 0.f) ? h_round16_with_c<BF>(val, beta, *(HGlbCU16)(uintptr_t)(C + offC)) : h_round16<BF>(val);
-            }
-        }
-    }
-
     // ---- beta != 0 with 16-byte lanes in C and D, one chunk at a time (gett_h16w4x_kernel's pipelined beta path) ----------------------
     // chunk IT (0 .. 7) of a pass of four parked 32 x 32 fragments (the layout of flush<.., NF = 4> below): fragment IT >> 1, 16-byte
     // chunk (IT & 1) * 64 + lane of its 128.  Compile-time chunk numbers and caller-named registers: an array of chunks indexed by a
@@ -324,13 +249,12 @@ struct HEpilogue {
         }
     }
 
-    // ---- four-fragment form (four-wave and streamed kernels) ------------------------------------------------------------
+    // ---- four-fragment form ---------------------------------------------------------------------------------------------
     // store the four parked fragments; fragment f covers rows mB + mHi (f >> 1) + mLo (f & 1) + [0, 32), columns alike
     // (base + steps, not arrays of four: a runtime-indexed array lands on the stack, and a scratch allocation is paid for at
     // every dispatch)
-    // ST (measurement): 0 = nontemporal stores, 1 = plain, 2 = write-through (sc1)
     // NF: fragments parked (4; 1: fragment 0 only — the 64 x 64 kernel's one fragment per wave)
-    template <bool BF, int ST = 0, int NF = 4>
+    template <bool BF, int NF = 4>
     __device__ __forceinline__ void flush(const GettParams& p, uint32_t mB0, uint32_t mHi, uint32_t mLo, uint32_t nB0, uint32_t nHi, uint32_t nLo, int lane) const {
         if (vecD) {
 #pragma unroll 2
@@ -358,9 +282,7 @@ struct HEpilogue {
                         }
                         out = h_round8_with_c<BF>(v0, v1, beta, cv);
                     } else out = h_round8<BF>(v0, v1);
-                    if constexpr (ST == 0) store16(D + offD, out, n);   // nontemporal: the result is not read again by this kernel
-                    else if constexpr (ST == 1) *(HGlbS8)(uintptr_t)(D + offD) = out;
-                    else asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(D + offD), "v"(out) : "memory");
+                    store16(D + offD, out, n);   // nontemporal: the result is not read again by this kernel
                 }
             }
             return;
@@ -387,15 +309,13 @@ struct HEpilogue {
 // ---------------------------------------------------------------------------------------------
 // One operand (A rows or B columns) of the streamed K-tile.
 // ---------------------------------------------------------------------------------------------
-// IL (the default kernel's B operand): half-tile h holds the 32-row stripes {64 j + 32 h + [0,32)}, j = 0..3, of the 256 rows
-// instead of rows 128 h + [0,128) — the two fragments a wave owns (stripe j = wc of either half) are then ADJACENT columns of
-// the output tile, and the epilogue stores whole 128-byte lines.
-// SWZ (free-contiguous image only; gett_h16w4x_kernel): unit p of k-row k holds row-unit p ^ 4 (k & 3) ^ 2 ((k >> 3) & 1) — the
-// 16-row fragments of the 16x16x32 MFMA take 32 bytes of a k-row per 16-lane group, and without the second term the two groups
-// that a transposing read serves together (k-rows 8 g + .. and 8 (g + 1) + ..) land on the same banks.
+// Free-contiguous image: unit p of k-row k holds row-unit p ^ 4 (k & 3) ^ 2 ((k >> 3) & 1) — the 16-row fragments of the 16x16x32 MFMA
+// take 32 bytes of a k-row per 16-lane group, and without the second term the two groups that a transposing read serves together
+// (k-rows 8 g + .. and 8 (g + 1) + ..) land on the same banks.
 // NH: half-tiles of 128 rows this operand stages per K-tile (2: the 256-row tiles; 1: the 128 x 128 mid-size kernel).
-template <int LAY, int NW = 8, bool IL = false, int SWZ = 0, int NH = 2>
+template <int LAY, int NH = 2>
 struct HOperand {
+    static constexpr int NW = 4;              // waves that stage a half-tile
     static constexpr int kPieces = 16 / NW;   // 1-KiB pieces of a half-tile this wave stages
     // Byte offset of this lane's 16-byte unit, [half-tile][piece i of this wave], for the K-tile at k = 0 — relative to
     // `base`, the smallest such offset in the wave: a workgroup tile spans far less than 2^32 bytes whatever the size of
@@ -414,13 +334,13 @@ struct HOperand {
                 if constexpr (LAY == LAY_K) {
                     const int r = 8 * c + (lane >> 3), p = lane & 7;
                     const int u = p ^ ((r >> 1) & 7);
-                    uint32_t row = row0 + (IL ? 64 * (r >> 5) + 32 * h + (r & 31) : 128 * h + r);
+                    uint32_t row = row0 + 128 * h + r;
                     if (row >= gFree.total) row = gFree.total - 1;   // clamped rows feed outputs that are never stored
                     off[h][i] = (group_offset<0>(gFree, row) + 8 * u) * 2;
                 } else {
                     const int kk = 4 * c + (lane >> 4), p = lane & 15;
-                    const int u = p ^ (4 * ((lane >> 4) & 3)) ^ (SWZ ? 2 * ((kk >> 3) & 1) : 0);
-                    uint32_t row = row0 + (IL ? 64 * (u >> 2) + 32 * h + 8 * (u & 3) : 128 * h + 8 * u);
+                    const int u = p ^ (4 * ((lane >> 4) & 3)) ^ (2 * ((kk >> 3) & 1));
+                    uint32_t row = row0 + 128 * h + 8 * u;
                     // a unit past the edge is clamped to the last one that holds rows of the mode (whole when extent % 8 == 0; a ragged
                     // extent — one M / N mode, pick_h16_choice — leaves a partial last unit whose dead rows feed outputs nobody stores)
                     if (row >= gFree.total) row = (gFree.total - 1u) & ~7u;
@@ -435,93 +355,22 @@ struct HOperand {
 #pragma unroll
             for (int i = 0; i < kPieces; ++i) src[h][i] = (uint32_t)(off[h][i] - mnW);
     }
-
-    // X: descriptor of (operand + batch offset + this wave's base + the K-tile's offset)
-    template <bool PAD = true>
-    __device__ __forceinline__ void issue(HRsrc X, int h, uint32_t slotByte, int wave) const {
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) h_dma16<PAD>(X, src[h][i], slotByte + (uint32_t)(wave + NW * i) * 1024u);
-    }
-    template <bool PAD = true>
-    __device__ __forceinline__ void issue_piece(HRsrc X, int h, int i, uint32_t slotByte, int wave) const {
-        h_dma16<PAD>(X, src[h][i], slotByte + (uint32_t)(wave + NW * i) * 1024u);
-    }
 };
 
-// Per-lane constant parts of the fragment addresses (bytes inside a half-tile slot).
-//   LAY_K: offK[s], s = 16-k step 0..3, for any 32-row fragment base rb: + rb * 128
-//   LAY_F: offF, depends on (rb >> 5) through the swizzle; + s * 4096 + h * 1024
-__device__ __forceinline__ uint32_t h_offK(int lane, int s) {
-    const int x0 = (lane >> 5) ^ ((lane >> 1) & 7);
-    return (uint32_t)((lane & 31) * 128 + (((x0 ^ (2 * s)) & 7) << 4));
-}
-__device__ __forceinline__ uint32_t h_offF(int lane, int rbq) {
-    const int g = lane >> 4, i = lane & 15;
-    const int kk = 8 * (g >> 1) + (i >> 2);
-    const int u = (((rbq ^ (i >> 2)) & 3) << 2) | (2 * (g & 1) + ((i >> 1) & 1));
-    return (uint32_t)(kk * 256 + (u << 4) + 8 * (i & 1));
-}
-
-template <int LAY>
-__device__ __forceinline__ s16x8 h_read_frag(const char* slot, int rb, int s, const uint32_t (&offK)[4], uint32_t offF) {
-    if constexpr (LAY == LAY_K) {
-        return *reinterpret_cast<const s16x8*>(slot + rb * 128 + offK[s]);
-    } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-        typedef s16x4 __attribute__((address_space(3))) * lptr;
-        const char* p = slot + s * 4096 + offF;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(p));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(p + 1024));
-        return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#else
-        (void)slot; (void)rb; (void)s; (void)offK; (void)offF; return s16x8{};
-#endif
-    }
-}
+// A table slot of a RETIRED family (gett_h16.hip: H16_W8 .. H16_W4R; gett_h16v.hip: H16_W4V).  Kernel indices are written into plan-cache
+// files, so the merged table keeps its length and order: the slot keeps the tile numbers, name and variant its entry always had, with
+// `ablation` = 2 ("not built", skipped by rank_h16_choices) and a launcher that answers hipErrorNotSupported.
+inline hipError_t launch_h16_not_built(const GettParams&, hipStream_t) { return hipErrorNotSupported; }
+#define CTAMD_H16_RETIRED(bk, wn, threads, pf, la, lb, kname, variant) \
+    {kHTile, kHTile, bk, 2, wn, 1, la, lb, threads, pf, 1, 2, &launch_h16_not_built, 0, 0, 0, 0, kname, variant},
+// eight entries per family: bf16 first, then fp16, each in the order (layA, layB) = (K,K) (K,F) (F,K) (F,F)
+#define CTAMD_H16_RETIRED8(bk, wn, threads, pf, kname, variant)                                                                               \
+    CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_K, LAY_K, kname, variant) CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_K, LAY_F, kname, variant) \
+    CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_F, LAY_K, kname, variant) CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_F, LAY_F, kname, variant) \
+    CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_K, LAY_K, kname, variant) CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_K, LAY_F, kname, variant) \
+    CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_F, LAY_K, kname, variant) CTAMD_H16_RETIRED(bk, wn, threads, pf, LAY_F, LAY_F, kname, variant)
 
 // (h_reload_params: gett_common.h reload_params)
 __device__ __forceinline__ void h_reload_params(GettParams& q) { reload_params(q); }
-
-// Wave-uniform walk over the K-tiles of the contraction: byte offsets of tile t in A and B.  Fast-K: the
-// fastest contracted digit's extent is a multiple of kHBK, so a tile never straddles a digit boundary.
-struct HOdometer {
-    uint32_t j0, n0, j1, e1, hi;
-    uint64_t offA, offB, stepA, stepB, wrapA, wrapB;      // bytes, modulo 2^64
-    __device__ static __forceinline__ uint32_t sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-    __device__ __forceinline__ void init(const ModeGroup& gK, uint32_t k0) {
-        const uint32_t E0 = gK.div[0].d;
-        n0 = sgpr(E0 / kHBK);
-        e1 = sgpr(gK.div[1].d);
-        const uint32_t q0 = (E0 < 2) ? k0 : fast_div(k0, gK.div[0]);
-        j0 = sgpr((k0 - q0 * E0) / kHBK);
-        hi = sgpr((e1 < 2) ? q0 : fast_div(q0, gK.div[1]));
-        j1 = sgpr(q0 - hi * e1);
-        offA = h_uniform64((uint64_t)(group_offset<0>(gK, k0) * 2));
-        offB = h_uniform64((uint64_t)(group_offset<1>(gK, k0) * 2));
-        stepA = h_uniform64((uint64_t)((int64_t)kHBK * gK.stride[0][0] * 2));
-        stepB = h_uniform64((uint64_t)((int64_t)kHBK * gK.stride[1][0] * 2));
-        wrapA = h_uniform64((uint64_t)(gK.stride[0][1] * 2) - (uint64_t)(n0 - 1) * stepA);
-        wrapB = h_uniform64((uint64_t)(gK.stride[1][1] * 2) - (uint64_t)(n0 - 1) * stepB);
-    }
-    __device__ __forceinline__ void carry(const ModeGroup& gK) {
-        const uint32_t k = hi * e1 * gK.div[0].d;
-        if (k < gK.total) {
-            offA = h_uniform64((uint64_t)(group_offset<0>(gK, k) * 2));
-            offB = h_uniform64((uint64_t)(group_offset<1>(gK, k) * 2));
-        }
-    }
-    __device__ __forceinline__ void advance(const ModeGroup& gK) {
-        const bool c0 = (j0 + 1 == n0);
-        j0 = c0 ? 0u : j0 + 1;
-        offA += c0 ? wrapA : stepA;
-        offB += c0 ? wrapB : stepB;
-        j1 += c0 ? 1u : 0u;
-        if (j1 == e1) {   // carry beyond the second digit (rare)
-            j1 = 0;
-            hi += 1;
-            carry(gK);
-        }
-    }
-};
 
 }  // namespace ctamd

@@ -37,7 +37,7 @@
 // Every other tile (edges, strided D, a C without the 16-byte lanes of D, batch modes, split-K partials) takes the epilogues of
 // gett_h16w4x_kernel, in the ring, and is set up and staged behind them — slower than the one-tile kernel, which is why the planner
 // offers this kernel only to problems whose interior tiles can stream and cutensorContract launches the one-tile twin for beta != 0 with
-// such a C (plan_contraction.cpp, api.cpp).  Roofline and algorithmic bytes as in gett_h16.hip (MFMA bf16; 2 M N K flop).
+// such a C (plan_contraction.cpp, api.cpp).  Roofline and algorithmic bytes as in gett_h16v.hip (MFMA bf16; 2 M N K flop).
 #include <type_traits>
 
 #include "gett_h16x_common.h"
@@ -152,8 +152,8 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4p_kernel(const GettParams p)
     }
 
     // ---- the tile in flight ------------------------------------------------------------------------------------------------
-    HOperand<LA, 4, false, 1> oa;
-    HOperand<LB, 4, false, 1> ob;
+    HOperand<LA> oa;
+    HOperand<LB> ob;
     VOdometer odo;
     uint32_t m0 = 0, n0 = 0, slice = 0, l = 0;
     int nTiles = 0;
@@ -651,7 +651,7 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4p_kernel(const GettParams p)
                         st[0] = ep.alpha * c[0]; st[32] = ep.alpha * c[1]; st[64] = ep.alpha * c[2]; st[96] = ep.alpha * c[3];
                     }
                 const uint32_t mB = mW + 32 * i;
-                ep.template flush<BF, 0>(pe, mB, 0u, 0u, nW, 64u, 32u, laneE);
+                ep.template flush<BF>(pe, mB, 0u, 0u, nW, 64u, 32u, laneE);
             }
         }
 #endif

@@ -1,10 +1,10 @@
-// gett_h16v.hip — the four-wave 16-bit GETT kernel with a LEAN instruction stream (CUTENSOR_AMD_H16_WAVES=4v; round 3).
+// gett_h16v.hip — the four-wave 16-bit GETT kernels with a LEAN instruction stream: gett_h16w4x_kernel (256 x 256 x 64, the family's
+// default), gett_h16w4m_kernel / gett_h16w8m_kernel (128 x 128 x 64) and gett_h16w4q_kernel (64 x 64 x 64).
 //
-// Same arithmetic, tile (256 x 256 x 64), LDS images, source-side swizzles, MFMA order, barrier placement and epilogue as
-// gett_h16w4_kernel (gett_h16.hip): 4 waves as 2 (M) x 2 (N), one per SIMD, a 128 x 128 quadrant each (4 x 4 accumulator
-// fragments, 256 AGPRs), two 64-deep K-tiles in LDS, ONE barrier per K-tile.  What changes is everything BETWEEN the MFMAs.
+// 16-bit data, fp32 accumulation on v_mfma_f32_16x16x32_{bf16,f16}; LDS-DMA staging with source-side swizzles, 64-deep K-tiles in an LDS
+// ring, ONE barrier per K-tile.  What the kernels share is everything BETWEEN the MFMAs.
 // With one wave per SIMD every instruction the wave issues sits in front of its own MFMAs (nothing else fills the issue slots),
-// and the matrix pipe only stays busy while at most ~6 other instructions separate two MFMAs.  The compiler's version of the
+// and the matrix pipe only stays busy while at most ~6 other instructions separate two MFMAs.  The compiler's version of a
 // four-wave loop carried ~230 non-MFMA instructions per K-tile (64 MFMAs), the vendor's hand-written kernel of the same
 // structure ~95 (NOTES.md, profiles/r03_h16_vendor_pmc_instruction_mix.txt).  Here:
 //   * LDS-DMA destination: M0 = (one SGPR: ring base + wave * 1 KiB) + a literal, formed by the s_add_u32 that writes M0 —
@@ -14,187 +14,18 @@
 //   * K odometer: the descriptor bases themselves advance (s_add_u32 / s_addc_u32 by a selected step), digit 0 by a countdown,
 //     and ONE countdown covers both rare events (carry past the second K digit, end of the K range: steps become zero);
 //     ~14 scalar instructions per K-tile spread over three MFMA pairs — instead of ~60 in one block behind a branch.
-// Roofline and algorithmic bytes as in gett_h16.hip.
+// Roofline: bf16/fp16 MFMA (4096 flop/clk/CU dense); algorithmic flops = 2*L*M*N*K, algorithmic bytes = |A| + |B| + |D| (16-bit
+// elements).  The table's first eight entries are the slots of gett_h16w4v_kernel, these kernels' retired 32x32x16 ancestor.
 #include <type_traits>
 
 #include "gett_h16x_common.h"
 
 namespace ctamd {
 
-#if defined(CTAMD_RESEARCH_KERNELS)   // gett_h16w4v_kernel: the 32x32x16 sibling of the default, retired in round 5 (research builds only)
-template <bool BF, int LA, int LB>
-__global__ void __launch_bounds__(256, 1) gett_h16w4v_kernel(const GettParams p) {
-    __shared__ __attribute__((aligned(16))) char lds[8 * kHalfBytes];
-    prefetch_kernarg<(int)sizeof(GettParams)>();
-    const int tid  = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-
-    uint32_t id = xcd_remap(blockIdx.x, p.nBlocks);
-    const uint32_t tilesMN = p.tilesM * p.tilesN;
-    const uint32_t tilesAll = tilesMN * p.gL.total;
-    const uint32_t slice = id / tilesAll;
-    id -= slice * tilesAll;
-    const uint32_t l = id / tilesMN;
-    id -= l * tilesMN;
-    const uint32_t perGroup = 8u * p.tilesN;
-    const uint32_t grp = id / perGroup, inGrp = id - grp * perGroup;
-    const uint32_t first = grp * 8u;
-    const uint32_t gsz = (p.tilesM - first < 8u) ? (p.tilesM - first) : 8u;
-    const uint32_t mt = first + inGrp % gsz, nt = inGrp / gsz;
-    const uint32_t m0 = mt * kHTile, n0 = nt * kHTile;
-    const uint32_t kTilesAll = p.gK.total / kHBK, tilesPerSlice = p.kPerSlice / kHBK;
-    const uint32_t tile0 = slice * tilesPerSlice;
-    const int nTiles = (int)((tile0 + tilesPerSlice <= kTilesAll) ? tilesPerSlice : (kTilesAll - tile0));
-
-    HOperand<LA, 4> oa;
-    HOperand<LB, 4> ob;
-    oa.init(p.gM, p.gK.stride[0][0], m0, wave, lane);
-    ob.init(p.gN, p.gK.stride[1][0], n0, wave, lane);
-    // descriptor base = operand + batch offset + this wave's smallest piece offset (+ the K-tile's offset: the odometer)
-    const uint64_t bA = h_uniform64((uint64_t)(uintptr_t)(static_cast<const uint16_t*>(p.A) + group_offset<0>(p.gL, l)) + oa.base);
-    const uint64_t bB = h_uniform64((uint64_t)(uintptr_t)(static_cast<const uint16_t*>(p.B) + group_offset<1>(p.gL, l)) + ob.base);
-    VOdometer odo;
-    odo.init(p.gK, tile0 * kHBK, (uint32_t)nTiles, bA, bB);
-
-    const uint32_t ldsBase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-    const uint32_t waveLds = VOdometer::sgpr(ldsBase + (uint32_t)wave * 1024u);
-
-    // fragment-read address registers: [buffer][k-step] for a K-contiguous operand (immediate: 4096 x fragment), [buffer][fragment]
-    // for a free-contiguous one (immediate: 4096 x k-step); opaque, so that they stay registers instead of becoming an add per read
-    uint32_t rdA[2][4], rdB[2][4];
-#pragma unroll
-    for (int P = 0; P < 2; ++P)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            rdA[P][x] = ldsBase + (uint32_t)((P * 4 + wr) * kHalfBytes) + (LA == LAY_K ? h_offK(lane, x) : h_offF(lane, x));
-            rdB[P][x] = ldsBase + (uint32_t)((P * 4 + 2 + wc) * kHalfBytes) + (LB == LAY_K ? h_offK(lane, x) : h_offF(lane, x));
-            asm volatile("" : "+v"(rdA[P][x]));
-            asm volatile("" : "+v"(rdB[P][x]));
-        }
-
-    // piece N = 0..15 of the K-tile the odometer describes, into buffer P: operand half q = N >> 2 (A0, A1, B0, B1), piece i = N & 3
-    // of this wave (1-KiB piece wave + 4 i of the half-tile)
-#define CTAMD_V_DMA(P, N, PAD)                                                                                      \
-    {                                                                                                              \
-        constexpr int q_ = (N) >> 2, i_ = (N) & 3;                                                                 \
-        constexpr uint32_t imm_ = (uint32_t)(((P) * 4 + q_) * kHalfBytes + i_ * 4096);                             \
-        if constexpr (q_ < 2) v_dma16<imm_, PAD>(v_rsrc(odo.addrA), oa.src[q_][i_], waveLds);                      \
-        else v_dma16<imm_, PAD>(v_rsrc(odo.addrB), ob.src[q_ - 2][i_], waveLds);                                   \
-    }
-#define CTAMD_V_DMA8(P, N0, PAD)                                                                                    \
-    CTAMD_V_DMA(P, (N0) + 0, PAD) CTAMD_V_DMA(P, (N0) + 1, PAD) CTAMD_V_DMA(P, (N0) + 2, PAD) CTAMD_V_DMA(P, (N0) + 3, PAD) \
-    CTAMD_V_DMA(P, (N0) + 4, PAD) CTAMD_V_DMA(P, (N0) + 5, PAD) CTAMD_V_DMA(P, (N0) + 6, PAD) CTAMD_V_DMA(P, (N0) + 7, PAD)
-#define CTAMD_V_ADVANCE() { odo.advance_a(); odo.advance_b(); odo.advance_event(p.gK); }
-
-    // ---- prologue: K-tile 0 complete, the first half of K-tile 1 ---------------------------------------------
-    CTAMD_V_DMA8(0, 0, true) CTAMD_V_DMA8(0, 8, true)
-    CTAMD_V_ADVANCE()
-    CTAMD_V_DMA8(1, 0, true)
-    CTAMD_H_VMCNT(8);                             // this wave's pieces of tile 0
-    __builtin_amdgcn_s_barrier();
-
-    f32x16 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    s16x8 a[2][4], b[2][4];                       // two register sets: k-step s uses set s & 1
-
-    // fragment F = 0..7 of k-step S from buffer P into register set SET: F < 4 -> B columns 32 F, else A rows 32 (F - 4)
-#define CTAMD_V_READ(P, S, SET, F)                                                                                  \
-    {                                                                                                              \
-        if constexpr ((F) < 4) {                                                                                   \
-            if constexpr (LB == LAY_K) b[SET][F] = v_read<LB, 4096 * (F)>(rdB[P][S]);                              \
-            else b[SET][F] = v_read<LB, 4096 * (S)>(rdB[P][F]);                                                    \
-        } else {                                                                                                   \
-            if constexpr (LA == LAY_K) a[SET][(F) - 4] = v_read<LA, 4096 * ((F) - 4)>(rdA[P][S]);                  \
-            else a[SET][(F) - 4] = v_read<LA, 4096 * (S)>(rdA[P][(F) - 4]);                                        \
-        }                                                                                                          \
-    }
-#define CTAMD_V_MFMA(SET, M) acc[(M) >> 2][(M) & 3] = h_mfma<BF>(a[SET][(M) >> 2], b[SET][(M) & 3], acc[(M) >> 2][(M) & 3]);
-    // k-step S < 3: one fragment read of step S + 1 per two MFMAs of step S.  k-step 0 also carries the second half (pieces
-    // 8..15) of the tile being staged into the other buffer; k-step 1 the odometer (three pairs)
-#define CTAMD_V_PAIR(P, S, F)                                                                                       \
-    CTAMD_V_READ(P, (S) + 1, ((S) + 1) & 1, F) CTAMD_V_MFMA((S) & 1, 2 * (F))                                      \
-    if constexpr ((S) == 0) CTAMD_V_DMA((P) ^ 1, 8 + (F), false)                                                   \
-    if constexpr ((S) == 1 && (F) == 1) odo.advance_a();                                                           \
-    if constexpr ((S) == 1 && (F) == 3) odo.advance_b();                                                           \
-    if constexpr ((S) == 1 && (F) == 5) odo.advance_event(p.gK);                                                   \
-    CTAMD_V_MFMA((S) & 1, 2 * (F) + 1)                                                                             \
-    __builtin_amdgcn_sched_barrier(0);
-#define CTAMD_V_STEP(P, S)                                                                                          \
-    CTAMD_V_PAIR(P, S, 0) CTAMD_V_PAIR(P, S, 1) CTAMD_V_PAIR(P, S, 2) CTAMD_V_PAIR(P, S, 3)                        \
-    CTAMD_V_PAIR(P, S, 4) CTAMD_V_PAIR(P, S, 5) CTAMD_V_PAIR(P, S, 6) CTAMD_V_PAIR(P, S, 7)
-    // k-step 3 (behind the barrier): reads of the next tile's step 0 (other buffer), the first half (pieces 0..7) of tile
-    // t + 2 into this buffer, MFMAs of step 3 — a read and a piece alternate, one per MFMA
-#define CTAMD_V_LAST2(P, F)                                                                                         \
-    CTAMD_V_READ((P) ^ 1, 0, 0, F)                                                                                 \
-    CTAMD_V_MFMA(1, 2 * (F)) __builtin_amdgcn_sched_barrier(0);                                                    \
-    CTAMD_V_DMA(P, F, false)                                                                                       \
-    CTAMD_V_MFMA(1, 2 * (F) + 1) __builtin_amdgcn_sched_barrier(0);
-#define CTAMD_V_TILE(P)                                                                                             \
-    CTAMD_V_STEP(P, 0) CTAMD_V_STEP(P, 1) CTAMD_V_STEP(P, 2)                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                                             \
-    CTAMD_H_LGKM0();                                                                                               \
-    CTAMD_H_VMCNT(0);                                                                                              \
-    __builtin_amdgcn_s_barrier();                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                                             \
-    CTAMD_V_LAST2(P, 0) CTAMD_V_LAST2(P, 1) CTAMD_V_LAST2(P, 2) CTAMD_V_LAST2(P, 3)                                \
-    CTAMD_V_LAST2(P, 4) CTAMD_V_LAST2(P, 5) CTAMD_V_LAST2(P, 6) CTAMD_V_LAST2(P, 7)
-
-    // first fragments of tile 0
-    CTAMD_V_READ(0, 0, 0, 0) CTAMD_V_READ(0, 0, 0, 1) CTAMD_V_READ(0, 0, 0, 2) CTAMD_V_READ(0, 0, 0, 3)
-    CTAMD_V_READ(0, 0, 0, 4) CTAMD_V_READ(0, 0, 0, 5) CTAMD_V_READ(0, 0, 0, 6) CTAMD_V_READ(0, 0, 0, 7)
-    int t = 0;
-    for (; t + 1 < nTiles; t += 2) { CTAMD_V_TILE(0) CTAMD_V_TILE(1) }
-    if (t < nTiles) { CTAMD_V_TILE(0) }
-    CTAMD_H_VMCNT(0);                             // the re-staged tail: no LDS-DMA may outlive the workgroup
-
-    const int laneE = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // fresh: nothing lane-derived lives across the loop for the epilogue
-    const uint32_t mW = m0 + 128 * wr, nW = n0 + 128 * wc;    // this wave's quadrant
-    if (p.partial != nullptr) {                   // split-K: fp32 partial tile, row-major [slice][l][m][n]
-        const uint32_t Mt = p.gM.total, Nt = p.gN.total;
-        float* P = p.partial + ((size_t)slice * p.gL.total + l) * (size_t)Mt * Nt;
-        auto store_partial = [&](const f32x16& c0, const f32x16& c1, const f32x16& c2, const f32x16& c3, uint32_t mBase) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const uint32_t m = mBase + (r & 3) + 8 * (r >> 2) + 4 * (laneE >> 5);
-                if (m < Mt) {
-                    const uint32_t n = nW + (laneE & 31);
-                    float* row = P + (size_t)m * Nt;
-                    if (n < Nt) row[n] = c0[r];
-                    if (n + 32 < Nt) row[n + 32] = c1[r];
-                    if (n + 64 < Nt) row[n + 64] = c2[r];
-                    if (n + 96 < Nt) row[n + 96] = c3[r];
-                }
-            }
-        };
-        store_partial(acc[0][0], acc[0][1], acc[0][2], acc[0][3], mW);
-        store_partial(acc[1][0], acc[1][1], acc[1][2], acc[1][3], mW + 32);
-        store_partial(acc[2][0], acc[2][1], acc[2][2], acc[2][3], mW + 64);
-        store_partial(acc[3][0], acc[3][1], acc[3][2], acc[3][3], mW + 96);
-        return;
-    }
-    __syncthreads();                              // every wave has finished reading the operand ring
-    HEpilogue ep;
-    ep.init(p, l, lds, wave);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {                 // four passes: the four fragments of accumulator row i
-        ep.park(0, acc[i][0], laneE); ep.park(1, acc[i][1], laneE); ep.park(2, acc[i][2], laneE); ep.park(3, acc[i][3], laneE);
-        const uint32_t mB = mW + 32 * i;
-        ep.template flush<BF>(p, mB, 0u, 0u, nW, 64u, 32u, laneE);
-    }
-}
-
-#endif  // CTAMD_RESEARCH_KERNELS
-
 // =====================================================================================================
-// gett_h16w4x_kernel (CUTENSOR_AMD_H16_WAVES=4x): the kernel above on v_mfma_f32_16x16x32_{bf16,f16}.
-// Why the other shape: under the power limit a stream of nothing but 16x16x32 MFMAs sustains 2.03-2.05 PFLOP/s on U(-1,1)
+// gett_h16w4x_kernel (CUTENSOR_AMD_H16_WAVES=4x): 4 waves as 2 (M) x 2 (N), one per SIMD, a 128 x 128 quadrant of the 256 x 256 tile
+// each, two 64-deep K-tiles in LDS (eight 16-KiB half-tile slots), on v_mfma_f32_16x16x32_{bf16,f16}.
+// Why this shape and not 32x32x16: under the power limit a stream of nothing but 16x16x32 MFMAs sustains 2.03-2.05 PFLOP/s on U(-1,1)
 // operands where 32x32x16 sustains 1.78-1.81 (tools/ubench/mfma16_issue.hip) — half the accumulator read-modify-write traffic
 // per flop (K = 32 per instruction).  The instruction is issued from inline asm: through the builtin the compiler's hazard
 // recognizer spaces independent 4-pass MFMAs 27 cycles apart instead of 16 (same microbenchmark), so the hazards are kept by
@@ -242,28 +73,11 @@ __device__ __forceinline__ void x_store_interior16(f32x4 (&acc)[FI][FJ], uint16_
     }
 }
 
-// TIMED (measurement-only instantiation, CUTENSOR_AMD_H16_TIMED=1 with the planner's default kernel, layout mk,kn): wave 0 of every
-// workgroup records shader cycles at entry / first MFMA / end of the main loop / exit and the wall clock at entry / exit into
-// p.timing (the layout tools/h16_wg_timeline.py reads).  XST (measurement, CUTENSOR_AMD_H16_XST, with TIMED only): 0 the default,
-// 1 plain instead of nontemporal stores in the epilogue, 3 always the fp32 LDS image (the general path) instead of the 16-bit one,
-// 4 the fragment reads of a k-step issued in its first eight groups (main loop 2280 -> 2415 cycles per K-tile), 5 first-round
-// workgroups start staggered (epilogue 16.4k -> 15.8k cycles, rate unchanged) — profiles/r04n_w4x_variants.jsonl.
-// XST = 8 / 9 / 10 (round 5, ZERO-FILLED operands only: the results are wrong on any other data — the tile barrier loses its
-// vmcnt(0) / its s_barrier / both): what of the 2280 - 2048 cycles per K-tile is data latency and what is wave skew.
 // RAG: ragged K — the last K-tile of the last slice staged with the lanes past the end of the contracted mode out of range
 // (x_rag_mask, gett_h16x_common.h); the offsets are switched right before the first LDS-DMA of that tile.
-template <bool BF, int LA, int LB, bool TIMED = false, int XST = 0, bool RAG = false>
+template <bool BF, int LA, int LB, bool RAG = false>
 __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p) {
     __shared__ __attribute__((aligned(16))) char lds[8 * kHalfBytes];
-    unsigned long long wgStamp[6] = {0, 0, 0, 0, 0, 0};
-    constexpr bool kEarly = (XST == 4);          // measurement: the 16 fragment reads of a k-step in its first 8 groups
-    if constexpr (XST == 5) {                    // measurement: first-round workgroups start up to 15 x 1024 cycles apart
-        if (blockIdx.x < 256u) {
-            const uint32_t steps = (blockIdx.x * 37u) & 15u;
-            for (uint32_t i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(16);
-        }
-    }
-    if constexpr (TIMED) { wgStamp[0] = __builtin_readcyclecounter(); wgStamp[4] = wall_clock64(); }
     prefetch_kernarg<(int)sizeof(GettParams)>();
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
@@ -290,8 +104,8 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
     const uint32_t tile0 = slice * tilesPerSlice;
     const int nTiles = (int)((tile0 + tilesPerSlice <= kTilesAll) ? tilesPerSlice : (kTilesAll - tile0));
 
-    HOperand<LA, 4, false, 1> oa;
-    HOperand<LB, 4, false, 1> ob;
+    HOperand<LA> oa;
+    HOperand<LB> ob;
     oa.init(p.gM, p.gK.stride[0][0], m0, wave, lane);
     ob.init(p.gN, p.gK.stride[1][0], n0, wave, lane);
     const uint64_t bA = h_uniform64((uint64_t)(uintptr_t)(static_cast<const uint16_t*>(p.A) + group_offset<0>(p.gL, l)) + oa.base);
@@ -410,8 +224,7 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
 #endif
     // k-step 0, group Q: one read of k-step 1 (same buffer) and four MFMAs; three of the groups carry the odometer
 #define CTAMD_X_G0(P, Q)                                                                                            \
-    if constexpr (!kEarly) CTAMD_X_READ(P, 1, Q)                                                                   \
-    if constexpr (kEarly && (Q) < 8) { CTAMD_X_READ(P, 1, 2 * ((Q) & 7)) CTAMD_X_READ(P, 1, 2 * ((Q) & 7) + 1) }   \
+    CTAMD_X_READ(P, 1, Q)                                                                                          \
     CTAMD_X_MFMA(0, 4 * (Q)) CTAMD_X_MFMA(0, 4 * (Q) + 1)                                                          \
     if constexpr ((Q) == 2) odo.advance_a();                                                                       \
     if constexpr ((Q) == 5) odo.advance_b();                                                                       \
@@ -421,8 +234,7 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
     // k-step 1 (behind the barrier), group Q: one read of the next tile's k-step 0 (other buffer), one piece of tile t + 2 into
     // this buffer, four MFMAs
 #define CTAMD_X_G1(P, Q)                                                                                            \
-    if constexpr (!kEarly) CTAMD_X_READ((P) ^ 1, 0, Q)                                                             \
-    if constexpr (kEarly && (Q) < 8) { CTAMD_X_READ((P) ^ 1, 0, 2 * ((Q) & 7)) CTAMD_X_READ((P) ^ 1, 0, 2 * ((Q) & 7) + 1) } \
+    CTAMD_X_READ((P) ^ 1, 0, Q)                                                                                    \
     CTAMD_X_MFMA(1, 4 * (Q)) CTAMD_X_MFMA(1, 4 * (Q) + 1)                                                          \
     CTAMD_X_DMA(P, Q, false)                                                                                       \
     CTAMD_X_MFMA(1, 4 * (Q) + 2) CTAMD_X_MFMA(1, 4 * (Q) + 3)                                                      \
@@ -433,8 +245,8 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
     CTAMD_X_G0(P, 12) CTAMD_X_G0(P, 13) CTAMD_X_G0(P, 14) CTAMD_X_G0(P, 15)                                        \
     CTAMD_X_RAGMASK(t + (P) + 2)     /* behind the odometer (k-step 0), in front of the pieces of tile t + 2 (k-step 1) */ \
     CTAMD_H_LGKM0();                                                                                               \
-    if constexpr (XST != 8 && XST != 10) CTAMD_H_VMCNT(0);                                                         \
-    if constexpr (XST != 9 && XST != 10) __builtin_amdgcn_s_barrier();                                             \
+    CTAMD_H_VMCNT(0);                                                                                              \
+    __builtin_amdgcn_s_barrier();                                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                             \
     CTAMD_X_RAGFIX(t + (P) + 1, (P) ^ 1)                                                                           \
     CTAMD_X_G1(P, 0) CTAMD_X_G1(P, 1) CTAMD_X_G1(P, 2) CTAMD_X_G1(P, 3) CTAMD_X_G1(P, 4) CTAMD_X_G1(P, 5)          \
@@ -446,13 +258,11 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
     CTAMD_X_READ(0, 0, 4) CTAMD_X_READ(0, 0, 5) CTAMD_X_READ(0, 0, 6) CTAMD_X_READ(0, 0, 7)
     CTAMD_X_READ(0, 0, 8) CTAMD_X_READ(0, 0, 9) CTAMD_X_READ(0, 0, 10) CTAMD_X_READ(0, 0, 11)
     CTAMD_X_READ(0, 0, 12) CTAMD_X_READ(0, 0, 13) CTAMD_X_READ(0, 0, 14) CTAMD_X_READ(0, 0, 15)
-    if constexpr (TIMED) wgStamp[1] = __builtin_readcyclecounter();
     int t = 0;
     for (; t + 1 < nTiles; t += 2) { CTAMD_X_TILE(0) CTAMD_X_TILE(1) }
     if (t < nTiles) { CTAMD_X_TILE(0) }
     CTAMD_H_VMCNT(0);                             // the re-staged tail: no LDS-DMA may outlive the workgroup
     x_acc_ready(acc);
-    if constexpr (TIMED) wgStamp[2] = __builtin_readcyclecounter();
     // the lane index again, from the hardware: nothing lane-derived stays live across the main loop for the epilogue's sake (one
     // spilled register = a scratch allocation at every dispatch)
     const int laneE = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -483,9 +293,7 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
     __syncthreads();                              // every wave has finished reading the operand ring
     HEpilogue ep;
     ep.init(pe, l, lds, wave);
-    unsigned long long tInit = 0, tWrite = 0;     // XST = 7 (measurement): cycles in HEpilogue::init and in the LDS-write phases
-    if constexpr (TIMED && XST == 7) tInit = __builtin_readcyclecounter() - wgStamp[2];
-    if (XST != 3 && ep.vecD && ep.beta == 0.f) {
+    if (ep.vecD && ep.beta == 0.f) {
         // beta == 0 and 16-byte lanes in D: the accumulators are rounded ONCE on their way into LDS (alpha * acc -> 16 bit), a pass of
         // 32 rows x 128 columns is an image of 272-byte rows (16 bytes of padding: the 2-byte writes of a 16-lane group and the
         // 16-byte reads of a row both spread over the banks), and the way out is eight 16-byte reads + nontemporal stores per lane —
@@ -517,8 +325,7 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
                         }
                     }
                     if (i > 0) {
-                        if constexpr (XST == 1) *reinterpret_cast<s16x8*>(dstI) = v[(i - 1) & 1][g];
-                        else __builtin_nontemporal_store(v[(i - 1) & 1][g], reinterpret_cast<s16x8*>(dstI));
+                        __builtin_nontemporal_store(v[(i - 1) & 1][g], reinterpret_cast<s16x8*>(dstI));
                         dstI += stepI;
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -532,8 +339,6 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
         } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            unsigned long long tw0 = 0;
-            if constexpr (TIMED && XST == 7) tw0 = __builtin_readcyclecounter();
 #pragma unroll
             for (int a2 = 0; a2 < 2; ++a2)
 #pragma unroll
@@ -543,7 +348,6 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
                     st[0] = h_round16<BF>(ep.alpha * c[0]); st[kPitch] = h_round16<BF>(ep.alpha * c[1]);
                     st[2 * kPitch] = h_round16<BF>(ep.alpha * c[2]); st[3 * kPitch] = h_round16<BF>(ep.alpha * c[3]);
                 }
-            if constexpr (TIMED && XST == 7) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tWrite += __builtin_readcyclecounter() - tw0; }
 #pragma unroll 4
             for (int it = 0; it < 8; ++it) {
                 const int q = it * 64 + laneE, row = q >> 4, cc = q & 15;
@@ -552,13 +356,12 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
                 if (m < ep.Mtot && n < ep.Ntot) {
                     int64_t offD, offC;
                     ep.offsets(pe, m, n, offD, offC);
-                    if constexpr (XST == 1) *reinterpret_cast<s16x8*>(ep.D + offD) = v;
-                    else ep.store16(ep.D + offD, v, n);
+                    ep.store16(ep.D + offD, v, n);
                 }
             }
         }
         }
-    } else if (XST == 0 && ep.vecD && ep.vecC && ep.beta != 0.f) {
+    } else if (ep.vecD && ep.vecC && ep.beta != 0.f) {
         // beta != 0 with 16-byte lanes in C and D: the fp32 image of the general path below (alpha acc + beta C is rounded ONCE), as a
         // software pipeline over the four passes of 32 rows.  vmcnt counts loads and stores in issue order, so a wave that asks for the C
         // chunks of a pass BEHIND the stores of the previous pass waits for those stores to be acknowledged before it may use the
@@ -603,40 +406,14 @@ __global__ void __launch_bounds__(256, 1) gett_h16w4x_kernel(const GettParams p)
                 st[0] = ep.alpha * c[0]; st[32] = ep.alpha * c[1]; st[64] = ep.alpha * c[2]; st[96] = ep.alpha * c[3];
             }
         const uint32_t mB = mW + 32 * i;
-        ep.template flush<BF, (XST == 1 ? 1 : 0)>(pe, mB, 0u, 0u, nW, 64u, 32u, laneE);
-    }
-    if constexpr (TIMED) {
-        if (p.timing != nullptr && wave == 0 && laneE == 0) {
-            wgStamp[3] = __builtin_readcyclecounter();            // the stores are issued, not waited for
-            wgStamp[5] = wall_clock64();
-#pragma unroll
-            for (int i = 0; i < 6; ++i) p.timing[64 + 8 * (size_t)blockIdx.x + i] = wgStamp[i];
-            p.timing[64 + 8 * (size_t)blockIdx.x + 6] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 0xf;   // HW_REG_XCC_ID
-            if constexpr (XST == 7) { p.timing[64 + 8 * (size_t)blockIdx.x + 1] = tInit; p.timing[64 + 8 * (size_t)blockIdx.x + 7] = tWrite; }
-        }
+        ep.template flush<BF>(pe, mB, 0u, 0u, nW, 64u, 32u, laneE);
     }
 }
 
 template <bool BF, int LA, int LB>
 static hipError_t launch_h16w4x(const GettParams& p, hipStream_t stream) {
-    const bool needRag = p.gK.total % (uint32_t)kHBK != 0u || (p.ragged & 1u) != 0u;   // (the TIMED / XST instantiations have no masked tile)
-#if defined(CTAMD_RESEARCH_KERNELS)
-    if constexpr (BF && LA == LAY_K && LB == LAY_F) if (!needRag) {   // the one instantiation that carries the in-kernel timestamps / store modes
-        static const bool timed = [] { const char* e = getenv("CUTENSOR_AMD_H16_TIMED"); return e && e[0] == '1'; }();
-        static const int xst = [] { const char* e = getenv("CUTENSOR_AMD_H16_XST"); return e ? atoi(e) : 0; }();
-        if (timed && xst == 1) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 1>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 3) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 3>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 4) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 4>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 5) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 5>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 7) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 7>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 8) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 8>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 9) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 9>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed && xst == 10) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true, 10>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-        if (timed) { hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-    }
-#endif
-    if (needRag) {   // ragged K (one contracted mode) or a unit that can straddle the tensor's end (pick_h16_choice): the masked last K-tile
-        hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, false, 0, true>), dim3(p.nBlocks), dim3(256), 0, stream, p);
+    if (p.gK.total % (uint32_t)kHBK != 0u || (p.ragged & 1u) != 0u) {   // ragged K (one contracted mode) or a unit that can straddle the tensor's end (pick_h16_choice): the masked last K-tile
+        hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB, true>), dim3(p.nBlocks), dim3(256), 0, stream, p);
         return hipGetLastError();
     }
     hipLaunchKernelGGL((gett_h16w4x_kernel<BF, LA, LB>), dim3(p.nBlocks), dim3(256), 0, stream, p);
@@ -695,8 +472,8 @@ __global__ void __launch_bounds__(256, (R == 2 ? 2 : 1)) gett_h16w4m_kernel(cons
     const uint32_t tile0 = slice * tilesPerSlice;
     const int nTiles = (int)((tile0 + tilesPerSlice <= kTilesAll) ? tilesPerSlice : (kTilesAll - tile0));
 
-    HOperand<LA, 4, false, 1, 1> oa;
-    HOperand<LB, 4, false, 1, 1> ob;
+    HOperand<LA, 1> oa;
+    HOperand<LB, 1> ob;
     oa.init(p.gM, p.gK.stride[0][0], m0, wave, lane);
     ob.init(p.gN, p.gK.stride[1][0], n0, wave, lane);
     const uint64_t bA = h_uniform64((uint64_t)(uintptr_t)(static_cast<const uint16_t*>(p.A) + group_offset<0>(p.gL, l)) + oa.base);
@@ -995,8 +772,8 @@ __global__ void __launch_bounds__(512, 1) gett_h16w8m_kernel(const GettParams p)
 
     if (mover) {
         // =========================== data movers ======================================================
-        HOperand<LA, 4, false, 1, 1> oa;
-        HOperand<LB, 4, false, 1, 1> ob;
+        HOperand<LA, 1> oa;
+        HOperand<LB, 1> ob;
         oa.init(p.gM, p.gK.stride[0][0], m0, wave, lane);
         ob.init(p.gN, p.gK.stride[1][0], n0, wave, lane);
         const uint64_t bA = h_uniform64((uint64_t)(uintptr_t)(static_cast<const uint16_t*>(p.A) + group_offset<0>(p.gL, l)) + oa.base);
@@ -1320,17 +1097,11 @@ __device__ __forceinline__ s16x8 q_read(uint32_t base) {
 #endif
 }
 
-// TIMED (measurement, CUTENSOR_AMD_H16_TIMED=1, bf16 mk,kn only): wave 0 records shader cycles at entry / first piece issued / tile 0
-// landed / end of the main loop / stores issued and the wall clock at entry / exit (tools/h16_small_timeline.py)
-// (An eight-deep ring, 128 KiB and one workgroup per CU, measured the same 460 cycles per K-tile at 1024^3 as this four-deep one and
-// a later first tile: a lone workgroup is not latency-bound either.  profiles/r04v_small_timeline.jsonl)
 // RAG: ragged K, as in gett_h16w4x_kernel (q_rag_mask): tile t stages tile t + 4 whole, one switch.
-template <bool BF, int LA, int LB, bool TIMED = false, bool RAG = false>
+template <bool BF, int LA, int LB, bool RAG = false>
 __global__ void __launch_bounds__(256, 2) gett_h16w4q_kernel(const GettParams p) {
     constexpr int R = 4;
     __shared__ __attribute__((aligned(16))) char lds[R * kQBuf];
-    unsigned long long qs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (TIMED) { qs[0] = __builtin_readcyclecounter(); qs[5] = wall_clock64(); }
     prefetch_kernarg<(int)sizeof(GettParams)>();
     // the arguments the setup reads, in ONE burst of scalar loads (through `p` they arrive one dependent round at a time)
     GettParams ps;
@@ -1362,7 +1133,6 @@ __global__ void __launch_bounds__(256, 2) gett_h16w4q_kernel(const GettParams p)
     const uint32_t kTilesAll = sweep ? (ps.ragged >> 2) : (ps.gK.total + (RAG ? (uint32_t)kHBK - 1u : 0u)) / kHBK, tilesPerSlice = ps.kPerSlice / kHBK;
     const uint32_t tile0 = slice * tilesPerSlice;
     const int nTiles = (int)((tile0 + tilesPerSlice <= kTilesAll) ? tilesPerSlice : (kTilesAll - tile0));
-    if constexpr (TIMED) { asm volatile("" :: "s"(nTiles), "s"(m0), "s"(n0)); qs[7] = __builtin_readcyclecounter(); }   // arguments fetched, tile located
 
     QOperand<LA> oa;
     QOperand<LB> ob;
@@ -1436,7 +1206,6 @@ __global__ void __launch_bounds__(256, 2) gett_h16w4q_kernel(const GettParams p)
 #define CTAMD_Q_NEXT() { odo.advance_a(); odo.advance_b(); odo.advance_event(p.gK); }
 
     // ---- prologue: K-tiles 0 .. R - 1; the odometer stays on tile R - 1 ----------------------------------------------------
-    if constexpr (TIMED) qs[1] = __builtin_readcyclecounter();
     CTAMD_Q_RAGMASK(0) CTAMD_Q_DMA4(0, true)
     CTAMD_Q_NEXT() CTAMD_Q_RAGMASK(1) CTAMD_Q_DMA4(1, true)
     CTAMD_Q_NEXT() CTAMD_Q_RAGMASK(2) CTAMD_Q_DMA4(2, true)
@@ -1444,7 +1213,6 @@ __global__ void __launch_bounds__(256, 2) gett_h16w4q_kernel(const GettParams p)
     CTAMD_H_VMCNT(4 * (R - 1));                   // this wave's pieces of tile 0
     __builtin_amdgcn_s_barrier();
     CTAMD_Q_RAGFIX(0, 0)
-    if constexpr (TIMED) qs[2] = __builtin_readcyclecounter();
 
     f32x4 acc[2][2];
 #pragma unroll
@@ -1486,12 +1254,11 @@ __global__ void __launch_bounds__(256, 2) gett_h16w4q_kernel(const GettParams p)
     if (t + 2 < nTiles) { CTAMD_Q_TILE(2) }
     CTAMD_H_VMCNT(0);                             // the re-staged tail: no LDS-DMA may outlive the workgroup
     x_acc_ready(acc);
-    if constexpr (TIMED) qs[3] = __builtin_readcyclecounter();
     const int laneE = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 
     const uint32_t mW = m0 + 32 * wr, nW = n0 + 32 * wc;      // this wave's quadrant
     // a fresh copy of the arguments for the epilogue, loaded in ONE burst (only the fields used): read through `p` the compiler fetches
-    // them one dependent s_load round at a time (~20 rounds, most of a 64 x 64 tile's epilogue: tools/h16_small_timeline.py)
+    // them one dependent s_load round at a time (~20 rounds, most of a 64 x 64 tile's epilogue: in-kernel stamps)
     GettParams pe;
     h_reload_params(pe);
     // accumulator fragment (i, j): element r of laneE = row 16 i + 4 (laneE >> 4) + r, column 16 j + (laneE & 15)
@@ -1552,28 +1319,14 @@ __global__ void __launch_bounds__(256, 2) gett_h16w4q_kernel(const GettParams p)
             const f32x4& c = acc[h >> 1][h & 1];
             st[0] = ep.alpha * c[0]; st[32] = ep.alpha * c[1]; st[64] = ep.alpha * c[2]; st[96] = ep.alpha * c[3];
         }
-        ep.template flush<BF, 0, 1>(pe, mW, 0u, 0u, nW, 0u, 0u, laneE);
-    }
-    if constexpr (TIMED) {
-        if (p.timing != nullptr && wave == 0 && laneE == 0) {
-            qs[4] = __builtin_readcyclecounter();                 // the stores are issued, not waited for
-            qs[6] = wall_clock64();
-#pragma unroll
-            for (int i = 0; i < 8; ++i) p.timing[64 + 8 * (size_t)blockIdx.x + i] = qs[i];
-        }
+        ep.template flush<BF, 1>(pe, mW, 0u, 0u, nW, 0u, 0u, laneE);
     }
 }
 
 template <bool BF, int LA, int LB>
 static hipError_t launch_h16w4q(const GettParams& p, hipStream_t stream) {
-#if defined(CTAMD_RESEARCH_KERNELS)
-    if constexpr (BF && LA == LAY_K && LB == LAY_F) {
-        static const bool timed = [] { const char* e = getenv("CUTENSOR_AMD_H16_TIMED"); return e && e[0] == '1'; }();
-        if (timed) { hipLaunchKernelGGL((gett_h16w4q_kernel<BF, LA, LB, true>), dim3(p.nBlocks), dim3(256), 0, stream, p); return hipGetLastError(); }
-    }
-#endif
     if (p.gK.total % (uint32_t)kHBK != 0u || (p.ragged & 1u) != 0u) {   // ragged K (one contracted mode) or a unit that can straddle the tensor's end (pick_h16_choice): the masked last K-tile
-        hipLaunchKernelGGL((gett_h16w4q_kernel<BF, LA, LB, false, true>), dim3(p.nBlocks), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((gett_h16w4q_kernel<BF, LA, LB, true>), dim3(p.nBlocks), dim3(256), 0, stream, p);
         return hipGetLastError();
     }
     hipLaunchKernelGGL((gett_h16w4q_kernel<BF, LA, LB>), dim3(p.nBlocks), dim3(256), 0, stream, p);
@@ -1582,13 +1335,7 @@ static hipError_t launch_h16w4q(const GettParams& p, hipStream_t stream) {
 
 template <bool BF, int LA, int LB>
 static hipError_t launch_h16w8m(const GettParams& p, hipStream_t stream) {
-#if defined(CTAMD_RESEARCH_KERNELS)
-    static const bool ring4 = [] { const char* e = getenv("CUTENSOR_AMD_H16_RING"); return e && e[0] == '4'; }();
-#else
-    static const bool ring4 = false;
-#endif   // measurement: the four-deep ring
-    if (ring4) hipLaunchKernelGGL((gett_h16w8m_kernel<BF, LA, LB, 4>), dim3(p.nBlocks), dim3(512), 0, stream, p);
-    else hipLaunchKernelGGL((gett_h16w8m_kernel<BF, LA, LB, 5>), dim3(p.nBlocks), dim3(512), 0, stream, p);
+    hipLaunchKernelGGL((gett_h16w8m_kernel<BF, LA, LB>), dim3(p.nBlocks), dim3(512), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -1602,20 +1349,7 @@ static hipError_t launch_h16w4m(const GettParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#if defined(CTAMD_RESEARCH_KERNELS)
-template <bool BF, int LA, int LB>
-static hipError_t launch_h16w4v(const GettParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL((gett_h16w4v_kernel<BF, LA, LB>), dim3(p.nBlocks), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
 // bf16 entries first, then fp16, each in the order (layA, layB) = (K,K) (K,F) (F,K) (F,F) — the order of gett_h16.hip's table
-#define CTAMD_H16W4V_ENTRY(bf, la, lb) \
-    {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 6, 1, 0, &launch_h16w4v<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4v_kernel", H16_W4V},
-#else
-static hipError_t launch_h16v_not_built(const GettParams&, hipStream_t) { return hipErrorNotSupported; }
-#define CTAMD_H16W4V_ENTRY(bf, la, lb) {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 6, 1, 2, &launch_h16v_not_built, 0, 0, 0, 0, "gett_h16w4v_kernel", H16_W4V},
-#endif
 #define CTAMD_H16W4X_ENTRY(bf, la, lb) \
     {kHTile, kHTile, kHBK, 2, 2, 1, la, lb, 256, 7, 1, 0, &launch_h16w4x<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4x_kernel", H16_W4X},
 #define CTAMD_H16W4M_ENTRY(bf, la, lb) \
@@ -1627,11 +1361,9 @@ static hipError_t launch_h16v_not_built(const GettParams&, hipStream_t) { return
 #define CTAMD_H16W4Q_ENTRY(bf, la, lb) \
     {kQTile, kQTile, kHBK, 2, 2, 1, la, lb, 256, 11, 1, 0, &launch_h16w4q<bf, la, lb>, 0, 0, 0, 0, "gett_h16w4q_kernel", H16_W4Q},
 static const GettKernelInfo g_h16v_table[] = {
-    CTAMD_H16W4V_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4V_ENTRY(true, LAY_K, LAY_F)
-    CTAMD_H16W4V_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4V_ENTRY(true, LAY_F, LAY_F)
-    CTAMD_H16W4V_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4V_ENTRY(false, LAY_K, LAY_F)
-    CTAMD_H16W4V_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4V_ENTRY(false, LAY_F, LAY_F)
-    // H16_W4X: the 16x16x32 form
+    // H16_W4V: the slots of the retired 32x32x16 sibling of the default (gett_h16_common.h)
+    CTAMD_H16_RETIRED8(kHBK, 2, 256, 6, "gett_h16w4v_kernel", H16_W4V)
+    // H16_W4X: the default 256 x 256 kernel
     CTAMD_H16W4X_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W4X_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W4X_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4X_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4X_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4X_ENTRY(false, LAY_K, LAY_F)
@@ -1646,7 +1378,7 @@ static const GettKernelInfo g_h16v_table[] = {
     CTAMD_H16W4M4_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W4M4_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W4M4_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W4M4_ENTRY(false, LAY_K, LAY_F)
     CTAMD_H16W4M4_ENTRY(false, LAY_F, LAY_K) CTAMD_H16W4M4_ENTRY(false, LAY_F, LAY_F)
-    // H16_W8M: 128 x 128, four multiplying + four data-moving waves, four-deep ring
+    // H16_W8M: 128 x 128, four multiplying + four data-moving waves, five-deep ring
     CTAMD_H16W8M_ENTRY(true, LAY_K, LAY_K) CTAMD_H16W8M_ENTRY(true, LAY_K, LAY_F)
     CTAMD_H16W8M_ENTRY(true, LAY_F, LAY_K) CTAMD_H16W8M_ENTRY(true, LAY_F, LAY_F)
     CTAMD_H16W8M_ENTRY(false, LAY_K, LAY_K) CTAMD_H16W8M_ENTRY(false, LAY_K, LAY_F)

@@ -1,4 +1,4 @@
-// gett_h16x_common.h — primitives shared by the lean four-wave 16-bit kernels (gett_h16v.hip: gett_h16w4v / w4x / w4m / w8m / w4q;
+// gett_h16x_common.h — primitives shared by the lean four-wave 16-bit kernels (gett_h16v.hip: gett_h16w4x / w4m / w8m / w4q;
 // gett_h16p.hip: the persistent gett_h16w4p_kernel): the LDS-DMA piece with a literal M0 offset, fragment reads with immediate
 // offsets, the K odometer over the descriptor bases, the inline-asm 16x16x32 MFMA and the fragment address maps.
 #pragma once
@@ -65,7 +65,7 @@ __device__ __forceinline__ s16x8 v_read(uint32_t base) {
 #endif
 }
 
-// K odometer over the descriptor bases (bytes).  K index = j0 * 64 + E0 * (j1 + e1 * hi) as in HOdometer; here digit 0 is a
+// K odometer over the descriptor bases (bytes).  K index = j0 * 64 + E0 * (j1 + e1 * hi); digit 0 is a
 // countdown and `untilEvent` counts the advances up to the next rare event.  Exactly nTiles - 1 advances move the bases
 // (K-tiles 1 .. nTiles - 1 of this workgroup's slice); any further call leaves them where they are (the last tile is re-staged,
 // never read).
@@ -318,7 +318,7 @@ __device__ __forceinline__ uint32_t x_offK(int lane, int s) {
     return (uint32_t)(row * 128 + (((unit ^ (row >> 1)) & 7) << 4));
 }
 
-// the same for a free-contiguous half-tile (image [64 k][128 rows], 256-byte k-rows, HOperand's SWZ = 1 form: unit p of k-row k holds
+// the same for a free-contiguous half-tile (image [64 k][128 rows], 256-byte k-rows, HOperand: unit p of k-row k holds
 // row-unit p ^ 4 (k & 3) ^ 2 ((k >> 3) & 1)): a 16-lane group g fetches the 4 k x 16 rows block (k = 8 g + [0,4), rows of fragment f)
 // that ds_read_b64_tr_b16 turns into "lane = row, four k"; the second read (+ 1024 B) brings k + 4.  The block is 32 contiguous
 // bytes in each of its four k-rows: quarter (f >> 1) ^ (k & 3) of the row, half (f & 1) ^ (g & 1) of the quarter — the groups g and

@@ -16,9 +16,9 @@ enum OperandLayout : int {
 // fp16, each in the order (layA, layB) = (K,K) (K,F) (F,K) (F,F) — and a variant's value is the table position of its first entry: the
 // table's order and length are fixed (kernel indices are written into plan-cache files), and this is where the order is written down.
 enum H16Variant : int {
-    H16_W8 = 0, H16_W4 = 8, H16_S = 16, H16_W4S = 24, H16_W4R = 32, H16_W4V = 40,   // retired families (research builds): eight waves in two
-                     // ping-pong rows; four waves, one per SIMD; eight / four free-running waves on a K-tile-32 ring; four waves
-                     // register-staged; four waves with the lean instruction stream (gett_h16v.hip)
+    H16_W8 = 0, H16_W4 = 8, H16_S = 16, H16_W4S = 24, H16_W4R = 32, H16_W4V = 40,   // retired families (slots without kernels): eight waves
+                     // in two ping-pong rows; four waves, one per SIMD; eight / four free-running waves on a K-tile-32 ring; four waves
+                     // register-staged; four waves with the lean instruction stream on the 32x32x16 MFMA
     H16_W4X  = 48,   // the lean four-wave kernel on the 16x16x32 MFMA: the default 256 x 256 kernel
     H16_W4M  = 56,   // 128 x 128 on a two-deep ring, two workgroups per CU
     H16_W4M4 = 64,   // 128 x 128 on a four-deep ring, one workgroup per CU
@@ -64,7 +64,7 @@ hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t st
 // streaming (LDS-DMA ring) kernels, gett_f32_stream.hip; gett_f32_kernels() returns the merged table
 const GettKernelInfo* gett_f32_stream_kernels(int* count);
 
-// bf16 / fp16 data, fp32 accumulation (v_mfma_f32_32x32x16_{bf16,f16}), gett_h16.hip
+// bf16 / fp16 data, fp32 accumulation (v_mfma_f32_16x16x32_{bf16,f16}): the merged table, gett_h16.hip
 const GettKernelInfo* gett_h16_kernels(int* count);
 const GettKernelInfo* gett_h16v_kernels(int* count);   // gett_h16v.hip: appended to the table above, H16_W4V .. H16_W4Q
 const GettKernelInfo* gett_h16p_kernels(int* count);   // gett_h16p.hip (persistent 256 x 256 kernel): H16_W4P

@@ -1564,7 +1564,7 @@ int ctamdMgDescribeKBoxes(int64_t extent, int64_t blockSize, int nDigits, const 
 // by a transfer whose event the piece's stream has waited for so far — a missing wait is an error even though the replay itself
 // is sequential.  Returns 0, or a negative code with a message in `err`.
 // ---------------------------------------------------------------------------------------------------------------------
-#if CTAMD_HOOKS_BUILT     // compiled into the hooks flavour (lib_hooks/) and research builds only: the production library has no test entry points
+#if CTAMD_HOOKS_BUILT     // compiled into the hooks flavour (lib_hooks/) only: the production library has no test entry points
 typedef struct { int32_t n; const int64_t* extent; const int64_t* stride; const int32_t* modes; } ctamdMgHostView;
 typedef int (*ctamdMgHostContractFn)(void* user, int dtype, const ctamdMgHostView* A, const void* a, const ctamdMgHostView* B, const void* b,
                                      const ctamdMgHostView* C, const void* c, void* d, double alpha, double beta);

@@ -238,7 +238,6 @@ for mA, mB in LAYOUTS:
 BY_ID = {c.id: c for c in CASES}
 IN_PROCESS = [c.id for c in CASES if c.group is None and not c.full_size]
 GROUPS = sorted({c.group for c in CASES if c.group})
-RESEARCH_GROUPS = ("korder", "h16_splitk1", "h16_splitk3", "h16_splitk8")      # switches that only a RESEARCH=1 build reads
 # the sweep problems of tests/test_gpu_contraction.py::test_every_candidate_kernel_and_split, and the one-tile shapes of its nontemporal twins
 SWEEP_PROBLEMS = [
     (dict(a=96, b=4, c=4, d=64, e=96), "dcba", "ebcd", "ea"), (dict(a=96, b=3, c=4, d=64, e=96), "dcba", "ebcd", "ea"),

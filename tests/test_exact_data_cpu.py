@@ -72,8 +72,6 @@ def test_every_case_plans_onto_its_path(lib):
 @pytest.mark.parametrize("group", xc.GROUPS)
 def test_every_switched_case_plans_onto_its_path(lib, group):
     ct, ops = lib
-    if group in xc.RESEARCH_GROUPS and not ct.lib.ctamdResearchKernelsBuilt():
-        pytest.skip("a retired kernel family: compiled by make RESEARCH=1 only (round 5)")
     cases = [c for c in xc.CASES if c.group == group]
     xc.in_child([c.id for c in cases], cases[0].env, timeout=300, mode="plan")
 

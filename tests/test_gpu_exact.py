@@ -22,8 +22,6 @@ import exact_data as xd
 
 pytestmark = pytest.mark.gpu
 
-RETIRED = "a retired kernel family: compiled by make RESEARCH=1 only (round 5)"
-
 
 @pytest.fixture(scope="module")
 def env(built):
@@ -59,8 +57,6 @@ def test_exact_under_a_switch(env, group):
     """the cases of one switch value in a fresh child (H16_WAVES = 4x .. 4q: every forced 16-bit kernel on four layouts x aligned, ragged K,
     sweep-ragged, no 16-byte lanes; the persistent kernel on a grid of 8; GEN = force / 0; PEEL = 0; REPACK = f; the in-launch fold)"""
     ct, ops, h, torch = env
-    if group in xc.RESEARCH_GROUPS and not ct.lib.ctamdResearchKernelsBuilt():
-        pytest.skip(RETIRED)
     xc._DATA.clear()
     cases = [c for c in xc.CASES if c.group == group]
     xc.in_child([c.id for c in cases], cases[0].env, timeout=TIMEOUTS.get(group, 900))

@@ -50,23 +50,13 @@ def _kernel_notes(co):
     return kernels
 
 
-def test_default_16_bit_kernels_use_no_scratch(built, tmp_path):
-    k = _kernel_notes(_code_object(tmp_path, "gett_h16"))
-    hot = {n: v for n, v in k.items() if "gett_h16_kernel" in n or "gett_h16s_kernel" in n}
-    if not hot:
-        pytest.skip("production build: the retired eight-wave families are compiled by make RESEARCH=1 only")
-    assert len(hot) >= 16, sorted(k)
-    bad = {n: v for n, v in hot.items() if v.get("private_segment_fixed_size", 0) or v.get("vgpr_spill_count", 0)}
-    assert not bad, bad
-
-
 def test_lean_four_wave_16_bit_kernels_use_no_scratch_and_all_512_registers(built, tmp_path):
-    """gett_h16v.hip: the default 16-bit kernel (gett_h16w4x_kernel, 16x16x32 MFMA) and its 32x32x16 sibling — one wave per SIMD,
-    256 accumulator registers + 256 others, no private segment (a scratch allocation is paid for at every dispatch)."""
+    """gett_h16v.hip: the default 16-bit kernel (gett_h16w4x_kernel, 16x16x32 MFMA) — one wave per SIMD, 256 accumulator registers
+    + 256 others, no private segment (a scratch allocation is paid for at every dispatch)."""
     k = _kernel_notes(_code_object(tmp_path, "gett_h16v"))
-    hot = {n: v for n, v in k.items() if "gett_h16w4x_kernel" in n or "gett_h16w4v_kernel" in n}
-    assert len(hot) >= 16, sorted(k)          # 8 layouts x types of the default and their ragged-K twins (+ 8 of the retired 32x32x16 sibling and the measurement-only instantiations in a research build)
-    assert sum(1 for n in hot if n.endswith("Lb0ELi0ELb1EEEvNS_10GettParamsE")) == 8, sorted(hot)   # <..., TIMED = false, XST = 0, RAG = true>
+    hot = {n: v for n, v in k.items() if "gett_h16w4x_kernel" in n}
+    assert len(hot) == 16, sorted(k)          # 8 layouts x types of the default and their ragged-K twins
+    assert sum(1 for n in hot if n.endswith("Lb1EEEvNS_10GettParamsE")) == 8, sorted(hot)   # <..., RAG = true>
     bad = {n: v for n, v in hot.items() if v.get("private_segment_fixed_size", 0) or v.get("vgpr_spill_count", 0)}
     assert not bad, bad
     assert all(v.get("group_segment_fixed_size", 131072) == 131072 for v in hot.values()), hot   # two K-tiles of 64 KiB
@@ -126,7 +116,7 @@ def test_fp32_stream_kernels_do_not_spill_vector_registers(built, tmp_path):
 
 @pytest.mark.parametrize("obj,symbol", [
     ("gett_f32_stream", "_ZN5ctamd22gett_f32_stream_kernelINS_9StreamCfgILi96ELi96ELi1ELi0ELi3ELi0ELb0EEEEEvNS_10GettParamsE"),
-    ("gett_h16v", "_ZN5ctamd18gett_h16w4x_kernelILb1ELi1ELi0ELb0ELi0ELb0EEEvNS_10GettParamsE"),
+    ("gett_h16v", "_ZN5ctamd18gett_h16w4x_kernelILb1ELi1ELi0ELb0EEEvNS_10GettParamsE"),
     ("gett_h16p", "_ZN5ctamd18gett_h16w4p_kernelILb1ELi1ELi0EEEvNS_10GettParamsE"),
 ])
 def test_argument_prefetch_keeps_one_register_per_touched_line(built, tmp_path, obj, symbol):

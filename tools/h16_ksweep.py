@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fixed vs per-K-tile cost of a 16-bit kernel variant: M = N = 8192, K swept (zero-filled or U(-1,1) operands).
-usage: [CUTENSOR_AMD_H16_WAVES=4|s] [CUTENSOR_AMD_H16_ABL=n] python tools/h16_ksweep.py [--zeros]"""
+usage: [CUTENSOR_AMD_H16_WAVES=4x|4p|4m|...] python tools/h16_ksweep.py [--zeros]"""
 import json
 import os
 import sys
@@ -32,6 +32,6 @@ for K in (64, 512, 2048, 8192):
     kn = p.describe()["kname"]
 per_tile_us = (rows[3][1] - rows[2][1]) * 1e3 / ((8192 - 2048) / 64) / 4      # 4 tile rounds per CU
 fixed_us = rows[2][1] * 1e3 / 4 - per_tile_us * 2048 / 64
-print(json.dumps({"kernel": kn, "zeros": zeros, "abl": os.environ.get("CUTENSOR_AMD_H16_ABL", "0"), "ms": rows,
+print(json.dumps({"kernel": kn, "zeros": zeros, "ms": rows,
                   "per_64k_tile_us": per_tile_us, "fixed_us_per_workgroup": fixed_us,
                   "per_tile_cycles_at_2p4GHz": per_tile_us * 2400}))

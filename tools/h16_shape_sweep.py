@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bf16 C[m,n] = A[m,k] B[k,n] over a list of shapes with whatever 16-bit kernel CUTENSOR_AMD_H16_WAVES selects (default: the
 planner's choice): one JSON line per shape (ms, TFLOP/s, kernel, split-K).  Used to check that a new default kernel does not lose on
-shapes other than the 8192^3 headline.  usage: [CUTENSOR_AMD_H16_WAVES=8] tools/h16_shape_sweep.py [--layout mk,kn]"""
+shapes other than the 8192^3 headline.  usage: [CUTENSOR_AMD_H16_WAVES=4m] tools/h16_shape_sweep.py [--layout mk,kn]"""
 import argparse
 import json
 import os

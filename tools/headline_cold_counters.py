@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """What bounds the headline einsum when its operands come from HBM (round-4 review item 6: "a 64- or 128-deep K-tile for the HBM-cold
-case ... or a measured negative with the counter that kills it").  Needs the RESEARCH build (make RESEARCH=1): the ablation
-instantiations of gett_f32_stream_kernel<96x96x32, ring 4, A K-contiguous, B free-contiguous> are planner candidates only there.
+case ... or a measured negative with the counter that kills it").  Needs the test-hooks flavour of the library (lib_hooks/): the ablation
+instantiations of gett_f32_stream_kernel<96x96x32, ring 4, A K-contiguous, B free-contiguous> are planner candidates only under
+CUTENSOR_AMD_ABLATION, which the production library does not read.
 For the default kernel, its nontemporal twin, ABL = 3 (full kernel + wait accounting), ABL = 2 (no MFMA: the memory path alone) and
 ABL = 1 (no refills: LDS + MFMA alone), each WARM (one operand pair, re-contracted out of the Infinity Cache) and COLD (four rotating
 pairs, 805 MB): us per GETT launch (fold off, HIP events over >= 300 launches) and, for ABL = 3, the mean cycles per workgroup
@@ -23,8 +24,8 @@ def main():
     os.environ["CUTENSOR_AMD_ABLATION"] = "1"
     import torch
     from cudalibrarysamples_amd import cutensor as ct, ops
-    if not ct.lib.ctamdResearchKernelsBuilt():
-        print(json.dumps({"error": "production build: the ablation candidates need make RESEARCH=1"}))
+    if not ct.lib.ctamdTestHooksBuilt():
+        print(json.dumps({"error": "production library: CUTENSOR_AMD_ABLATION is read by the test-hooks flavour (lib_hooks/) only"}))
         return 1
     ext = dict(a=96, b=64, c=64, d=64, e=96)
     mA, mB, mC = "dcba", "ebcd", "ea"
