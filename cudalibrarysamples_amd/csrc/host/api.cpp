@@ -159,7 +159,8 @@ bool plan_env_override() {
     return CTAMD_HOOK_ENV("CUTENSOR_AMD_FORCE") || CTAMD_HOOK_ENV("CUTENSOR_AMD_XCD_BALANCE") || CTAMD_HOOK_ENV("CUTENSOR_AMD_FUSED_FOLD") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_TRANSPOSE_T1") || CTAMD_HOOK_ENV("CUTENSOR_AMD_NT") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_SPLITK") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER") || CTAMD_HOOK_ENV("CUTENSOR_AMD_ABLATION") || CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") || CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") ||
-           CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X");
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X") ||
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_F64X");
 }
 
 double scalar_as_double(const void* s, hipDataType t) {   // real part for complex scalar types
@@ -459,6 +460,55 @@ static bool f32x_decide(const ContractionView& v, int elem, uint64_t wsLimit, in
     else if (!(g.estimateUs < 0.8 * t32)) why = "model sees no gain";
     std::snprintf(buf, sizeof buf, "%s (model: reduced-precision %.1f us, fp32 plan %.1f us)%s%s", why ? "fp32 kernels kept" : "reduced-precision kernels",
                   g.estimateUs, t32, why ? ": " : "", why ? why : "");
+    note = buf;
+    return why == nullptr;
+}
+// ---- COMPUTE_DESC_32F on fp64 / complex128 data (kernels/gett_gen_f64x.inc) ----------------------------------------------------
+namespace ctamd { thread_local int t_f64xOff = 0; }
+// On a contraction whose tensors are all real fp64 (all complex128) with double (complex double) scalars the descriptor PERMITS
+// products of operands rounded once to fp32, on the fp32 MFMA; the fp64 kernels stay a legal answer.  Returns the general family's
+// element for the descriptor, or -1 when the contraction is not of that kind.
+static int f64x_elem_of(const cutensorOperationDescriptor& d) {
+    if (d.kind != OpKind::Contraction || d.compute == nullptr || d.compute->id != 4) return -1;
+    const hipDataType t = d.A.desc.dtype;
+    if ((t != HIP_R_64F && t != HIP_C_64F) || d.scalarType != t) return -1;
+    for (const TensorUse* u : {&d.A, &d.B, &d.C, &d.D})
+        if (u->present && u->desc.dtype != t) return -1;
+    return t == HIP_R_64F ? GEN_F64_F32 : GEN_C64_C32;
+}
+// CUTENSOR_AMD_F64X (test-hooks flavour): "force" — the single-precision kernels whenever the descriptor permits them; "0" — never
+static int f64x_switch() {
+    const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_F64X");
+    return (e == nullptr) ? 0 : (e[0] == 'f') ? 1 : (e[0] == '0') ? -1 : 0;
+}
+// Whether a plan for view `v` (fp64 / complex128 data, descriptor element `elem`) takes the single-precision kernels: `g` is their
+// choice, compared with the fp64 plan pick_gen_choice gives the same view.  By the model, only problems it can place: 16-byte loads on
+// both operands, no split-K on either side, at least one output tile per CU, and an estimate below 0.8 x the fp64 plan's — both from
+// gen_f64_measured_estimate_us (plan_contraction.cpp): one formula, each side at its measured rate.  `note` says
+// which side won and on what numbers (the CUTENSOR_LOG_LEVEL plan line).
+static bool f64x_decide(const ContractionView& v, int elem, uint64_t wsLimit, int numCUs, bool explicitPick, ContractionChoice& g, std::string& note) {
+    const int sw = f64x_switch();
+    char buf[256];
+    if (elem < 0 || v.wide || explicitPick || t_inRepack || t_f64xOff > 0 || sw < 0) return false;
+    if (!pick_gen_choice(v, wsLimit, numCUs, g, elem)) { note = "no single-precision kernel for this view -> fp64 kernels"; return false; }
+    ContractionChoice g64;
+    const bool have64 = pick_gen_choice(v, wsLimit, numCUs, g64);
+    const double t64 = have64 ? gen_f64_measured_estimate_us(v, g64, numCUs) : -1.0;
+    if (sw > 0) {
+        std::snprintf(buf, sizeof buf, "single-precision kernels forced (model %.1f us, fp64 plan %.1f us)", g.estimateUs, t64);
+        note = buf;
+        return true;
+    }
+    const GettKernelInfo& k = *kernel_info(2, g.kernel);
+    const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
+    const char* why = nullptr;
+    if (!have64) why = "no fp64 MFMA plan to compare with";
+    else if (elem == GEN_F64_F32 && k.vec != 2) why = "element gathers";
+    else if (g.splitK > 1 || g64.splitK > 1) why = "split-K problem";
+    else if (tiles < (double)numCUs) why = "fewer output tiles than CUs";
+    else if (!(g.estimateUs < 0.8 * t64)) why = "model sees no gain";
+    std::snprintf(buf, sizeof buf, "%s (model: single-precision %.1f us, fp64 plan %.1f us)%s%s", why ? "fp64 kernels kept" : "single-precision kernels",
+                  g.estimateUs, t64, why ? ": " : "", why ? why : "");
     note = buf;
     return why == nullptr;
 }
@@ -1126,6 +1176,13 @@ static cutensorStatus_t estimate_contraction(const cutensorHandle_t handle, cute
     }
     if (v.dtype == HIP_R_64F || v.dtype == HIP_C_32F || v.dtype == HIP_C_64F) {   // split-K partials of the general MFMA family
         ContractionChoice gc;
+        // COMPUTE_DESC_32F on fp64 / complex128 data: the same decision as rank_tiled_candidates — the fp32 partials of that kernel
+        std::string note;
+        if (!CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0') &&
+            f64x_decide(v, f64x_elem_of(desc), cap, numCUs, planPref != nullptr && names_candidate_or_tunes(*planPref), gc, note)) {
+            *estimate = gc.workspace;
+            return CUTENSOR_STATUS_SUCCESS;
+        }
         if (!pick_gen_choice(v, cap, numCUs, gc)) return CUTENSOR_STATUS_SUCCESS;
         *estimate = gc.workspace;
         // fp64 on element gathers: an operand copied first when that pays (plan_repack)
@@ -1164,6 +1221,7 @@ cutensorStatus_t cutensorEstimateWorkspaceSize(const cutensorHandle_t handle, co
     if (desc->kind == OpKind::ContractionTrinary) {   // intermediate + the larger of the two pairwise needs
         uint64_t w1 = 0, w2 = 0;
         cutensorOperationDescriptor s1 = desc->sub[0], s2 = desc->sub[1];
+        F64xOffScope fullPrecision;
         cutensorStatus_t st = estimate(s1, w1);
         if (st == CUTENSOR_STATUS_SUCCESS) st = estimate(s2, w2);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
@@ -1413,6 +1471,7 @@ static cutensorStatus_t build_trinary(const PlanRequest& rq, cutensorPlan& pl) {
     const uint64_t tOff = align256(desc.tBytes);
     if (rq.wsLimit < tOff) { CT_LOG("cutensorCreatePlan: trinary contraction needs %llu bytes for its intermediate", (unsigned long long)tOff); return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE; }
     cutensorOperationDescriptor s1 = desc.sub[0], s2 = desc.sub[1];
+    F64xOffScope fullPrecision;
     cutensorStatus_t st = create_sub_plan(rq, s1, rq.wsLimit - tOff, pl.sub1);
     if (st == CUTENSOR_STATUS_SUCCESS) st = create_sub_plan(rq, s2, rq.wsLimit - tOff, pl.sub2);
     if (st != CUTENSOR_STATUS_SUCCESS) return st;
@@ -1565,6 +1624,17 @@ static TiledRoute rank_tiled_candidates(const PlanRequest& rq, const cutensorPla
             r.tDirectUs = 0.0;
         }
         if (xe >= 0 && !note.empty()) CT_LOG("plan: fp32 contraction, compute descriptor %s: %s", xe == GEN_F32_F16 ? "16F" : xe == GEN_F32_BF16 ? "16BF" : "TF32", note.c_str());
+    }
+    if (r.genPath && !r.h16Path) {
+        // COMPUTE_DESC_32F on fp64 / complex128 data: the fp32-rate kernels when the model (or CUTENSOR_AMD_F64X=force) says so.  They take
+        // the operands as they lie (no repack pre-pass); a caller who names a candidate gets the fp64 plan as ever.
+        const int xe = f64x_elem_of(desc);
+        ContractionChoice gx;
+        std::string note;
+        if (xe >= 0 && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0') && f64x_decide(v, xe, rq.wsLimit, numCUs, names_candidate_or_tunes(rq.pr), gx, note))
+            r.ch.assign(1, gx);
+        if (xe >= 0 && !note.empty()) CT_LOG("plan: %s contraction, compute descriptor 32F: %s", xe == GEN_F64_F32 ? "fp64" : "complex128", note.c_str());
+        if (!r.ch.empty()) return r;
     }
     if ((v.dtype == HIP_R_64F || v.dtype == HIP_C_32F) && desc.scalarType == v.dtype && r.genPath && r.ch.empty()) {   // fp64 / complex64 on element gathers (plan_repack)
         ContractionChoice g64;
@@ -1813,7 +1883,7 @@ cutensorStatus_t cutensorCreatePlan(const cutensorHandle_t handle, cutensorPlan_
     PlanMemoKey mkey;
     uint64_t mhash = 0;
     const bool memoable = handle->planCacheCapacity > 0 && pr.cacheMode != CUTENSOR_CACHE_MODE_NONE && !plan_env_override() &&
-                          build_memo_key(*desc, pr, workspaceSizeLimit, mkey);
+                          !(t_f64xOff > 0 && f64x_elem_of(*desc) >= 0) && build_memo_key(*desc, pr, workspaceSizeLimit, mkey);
     if (memoable) {
         mhash = mkey.hash();
         if (handle->pendingCount.load(std::memory_order_relaxed) > 0) resolve_pending_measurements(handle);

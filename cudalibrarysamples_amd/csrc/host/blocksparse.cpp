@@ -73,6 +73,7 @@ static void block_shape(const cutensorBlockSparseTensorDescriptor& T, uint64_t b
 // Enumerates the block pairs and builds (or only sizes, when handle plans are not wanted) the dense plans.
 static cutensorStatus_t build_blocksparse(cutensorHandle_t handle, const BlockSparseOp& op, uint64_t wsLimit, bool makePlans,
                                           BlockSparsePlan* out, uint64_t* workspace) {
+    F64xOffScope fullPrecision;      // the block pairs' plans keep fp64 under COMPUTE_DESC_32F
     auto find = [](const std::vector<int32_t>& v, int32_t l) { for (size_t i = 0; i < v.size(); ++i) if (v[i] == l) return (int)i; return -1; };
     if (op.mC != op.mD) return CUTENSOR_STATUS_NOT_SUPPORTED;
     // index of the D block with given per-mode sections

@@ -138,6 +138,9 @@ std::vector<ContractionChoice> rank_contraction_choices(const ContractionView& v
 bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c);
 // general MFMA family (kernels/gett_gen.inc): false only for fp32 data and for views the tiled kernels cannot describe
 // (f32xElem: fp32 data under a reduced-precision compute descriptor — GEN_F32_BF16 / GEN_F32_F16 / GEN_F32_BF16X3, gett_gen_f32x.inc)
+// what f64x_decide compares: an fp64 / complex128 plan of the general family, or its single-precision twin, at its measured rate
+double gen_f64_measured_estimate_us(const ContractionView& v, const ContractionChoice& c, int numCUs);
+// (or fp64 / complex128 data under COMPUTE_DESC_32F — GEN_F64_F32 / GEN_C64_C32, gett_gen_f64x.inc)
 bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c, int f32xElem = -1);
 // 16-bit family: the default kernel variant first, then the other variants of the same tile / split (the candidates
 // CUTENSOR_ALGO_DEFAULT_PATIENT and incremental autotuning measure)
@@ -188,6 +191,10 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
 cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t wsLimit, int numCUs,
                                 ReducePlan& plan, std::string* why);
 
+// Raised while the pairwise plans of a trinary or a block-sparse contraction are made or priced: under COMPUTE_DESC_32F on fp64 /
+// complex128 data those keep the fp64 kernels (f64x_decide, api.cpp), and the plan memo stands aside for them
+extern thread_local int t_f64xOff;
+struct F64xOffScope { F64xOffScope() { ++t_f64xOff; } ~F64xOffScope() { --t_f64xOff; } };
 cutensorStatus_t blocksparse_estimate(cutensorHandle_t handle, const cutensorOperationDescriptor& desc, uint64_t* ws);
 cutensorStatus_t blocksparse_plan(cutensorHandle_t handle, const cutensorOperationDescriptor& desc, uint64_t wsLimit, cutensorPlan* pl);
 int blocksparse_describe(const cutensorPlan& pl, char* buf, size_t len);   // ctamdDescribePlan of a block-sparse plan

@@ -715,6 +715,13 @@ std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64
 // ---------------------------------------------------------------------------------------------
 // efficiency of the reduced-precision fp32 kernels against their MFMA ceiling (one product per k-block / three): see pick_gen_choice
 static constexpr double kF32xEffX1 = 0.18, kF32xEffX3 = 0.275;
+// efficiency of the single-precision-compute fp64 / complex128 kernels (gett_gen_f64x.inc) against the 157.3 TFLOP/s of
+// v_mfma_f32_16x16x4_f32: the forced kernel's rate at 4096^3 (complex: 2048^3), 'mk,kn', median of five alternated runs —
+// 103.7 TFLOP/s for fp64 data, 105.1 for complex128 (profiles/f64x_compute.jsonl, the "summary" record): see pick_gen_choice
+static constexpr double kF64xEffReal = 0.66, kF64xEffCplx = 0.67;
+// ... and what the fp64 kernels of this family sustain of THEIR MFMA rate where they stage 16-byte units: 60-63 of 78.6 TFLOP/s at fp64
+// 4096^3, 62 at complex128 2048^3
+static constexpr double kF64GenEff = 0.78;
 
 static int gen_elem_of(hipDataType t) {
     switch (t) {
@@ -750,11 +757,14 @@ static int gen_operand_vec(const ContractionView& v, bool slotA, int orient, int
 }
 
 bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c, int f32xElem) {
-    // fp32 data enters this family only under a reduced-precision compute descriptor (f32xElem: GEN_F32_BF16 / _F16 / _BF16X3)
-    const int elem = (v.dtype == HIP_R_32F) ? (gen_elem_is_f32x(f32xElem) ? f32xElem : -1) : gen_elem_of(v.dtype);
+    // fp32 data enters this family only under a reduced-precision compute descriptor (f32xElem: GEN_F32_BF16 / _F16 / _BF16X3);
+    // fp64 / complex128 data takes the single-precision-compute kernels when the caller names their element (GEN_F64_F32 / GEN_C64_C32)
+    const int elem = (v.dtype == HIP_R_32F) ? (gen_elem_is_f32x(f32xElem) ? f32xElem : -1)
+                   : (v.dtype == HIP_R_64F && f32xElem == GEN_F64_F32) || (v.dtype == HIP_C_64F && f32xElem == GEN_C64_C32) ? f32xElem
+                   : gen_elem_of(v.dtype);
     if (elem < 0 || v.wide) return false;
-    const bool f32x = gen_elem_is_f32x(elem);
-    const int maxV = (elem == GEN_C64) ? 1 : (elem == GEN_F64 || elem == GEN_C32) ? 2 : f32x ? 4 : 8;
+    const bool f32x = gen_elem_is_f32x(elem), f64x = gen_elem_is_f64x(elem);
+    const int maxV = (elem == GEN_C64 || elem == GEN_C64_C32) ? 1 : (elem == GEN_F64 || elem == GEN_C32 || elem == GEN_F64_F32) ? 2 : f32x ? 4 : 8;
     int orient[2], vec[2];
     for (int o = 0; o < 2; ++o) {
         const bool slotA = o == 0;
@@ -793,8 +803,8 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     const double tiles = tiles_of(c.kernel);
     const uint64_t kTiles = (v.totK + k.bk - 1) / k.bk;
     // split-K when the output tiles alone leave most CUs idle: partial tiles [slice][L][M][N] in the accumulator type
-    // (fp32 for 16-bit data, double / float2 / double2 for fp64 / complex64 / complex128)
-    const uint64_t accBytes = gen_elem_f32_partials(elem) ? 4ull : (elem == GEN_C64) ? 16ull : 8ull;
+    // (fp32 for 16-bit data, double / float2 / double2 for fp64 / complex64 / complex128; fp32 / float2 for those two under COMPUTE_DESC_32F)
+    const uint64_t accBytes = gen_elem_partial_bytes(elem);
     const uint64_t perSliceBytes = v.totL * v.totM * v.totN * accBytes;
     // From 16 K-tiles on, slices of at least four.  (Round 4 raised this to 48 K-tiles on a misread pair of numbers; the records say the
     // opposite — the reference's fp16 case 'mlik,lkjm->lij', 50 batches x 32 K-tiles on 2-byte gathers: 19.2 us in five slices
@@ -814,8 +824,8 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     c.kPerSlice = (uint32_t)(tilesPerSlice * k.bk);
     c.workspace = (c.splitK > 1) ? (uint64_t)c.splitK * perSliceBytes : 0ull;
     // rough time: the family's MFMA rate for the type at ~50 % utilisation (only used for logs / describe)
-    const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32) ? 256.0 : f32x ? (elem == GEN_F32_BF16X3 ? 4096.0 / 3.0 : 4096.0) : 128.0;
-    const double flops = ((elem == GEN_C32 || elem == GEN_C64) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
+    const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32 || f64x) ? 256.0 : f32x ? (elem == GEN_F32_BF16X3 ? 4096.0 / 3.0 : 4096.0) : 128.0;
+    const double flops = ((elem == GEN_C32 || elem == GEN_C64 || elem == GEN_C64_C32) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
     c.estimateUs = std::ceil(tiles * c.splitK / (double)numCUs) * flops / (flopPerClkCU * 2.4e9 * 0.5) * 1e6 + 2.0;
     if (f32x) {
         // The estimate that decides between these kernels and the ranked fp32 candidates (cutensorCreatePlan).  Waves of workgroups at
@@ -828,7 +838,30 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         const double bytes = 4.0 * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
         c.estimateUs = std::max(tCompute, bytes / 4.0e12 * 1e6) + 4.0;
     }
+    if (f64x) c.estimateUs = gen_f64_measured_estimate_us(v, c, numCUs);
     return true;
+}
+
+// The estimate on which f64x_decide (api.cpp) compares an fp64 / complex128 plan of this family with its single-precision twin: ONE
+// formula for both sides, each at its measured rate.  Waves of workgroups x the tile's flops / (the element's MFMA rate x its measured
+// efficiency: kF64GenEff for the fp64 kernels, kF64xEffReal / kF64xEffCplx for the fp32-rate ones), never below what moving the operands
+// and the output once at 4 TB/s costs, + 2 us for the launch.  (ContractionChoice::estimateUs of an fp64 plan stays the figure for logs
+// it was, at a flat 50 %: 1.6 x the measured time.)  Negative: `c` is not such a plan.
+double gen_f64_measured_estimate_us(const ContractionView& v, const ContractionChoice& c, int numCUs) {
+    const GettKernelInfo* tab = nullptr;
+    int count = 0;
+    tab = gett_gen_kernels(&count);
+    if (c.family != 2 || c.kernel < 0 || c.kernel >= count) return -1.0;
+    const GettKernelInfo& k = tab[c.kernel];
+    const bool f64x = gen_elem_is_f64x(k.elem);
+    if (!f64x && k.elem != GEN_F64 && k.elem != GEN_C64) return -1.0;
+    const bool cplx = k.elem == GEN_C64 || k.elem == GEN_C64_C32;
+    const double rate = (f64x ? 256.0 : 128.0) * 2.4e9 * (!f64x ? kF64GenEff : cplx ? kF64xEffCplx : kF64xEffReal);      // flop / s / CU
+    const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
+    const double flops = (cplx ? 8.0 : 2.0) * k.bm * k.bn * (double)(c.kPerSlice ? c.kPerSlice : v.totK);
+    const double tCompute = std::ceil(tiles * std::max<uint32_t>(c.splitK, 1u) / (double)numCUs) * flops / rate * 1e6;
+    const double bytes = (double)dtype_size(v.dtype) * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
+    return std::max(tCompute, bytes / 4.0e12 * 1e6) + 2.0;
 }
 
 static void fill_group(ModeGroup& g, const std::vector<CanonMode>& modes) {

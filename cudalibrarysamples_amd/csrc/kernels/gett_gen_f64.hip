@@ -65,6 +65,7 @@ __global__ void __launch_bounds__(256) gen_splitk_reduce_kernel(const SplitKRedu
 hipError_t launch_gen_splitk_reduce(const SplitKReduceParams& p, int elem, hipStream_t stream) {
     const size_t total = (size_t)p.gM.total * p.gN.total * p.gL.total;
     if (total == 0) return hipSuccess;
+    if (gen_elem_is_f64x(elem)) return launch_gen_f64x_splitk_reduce(p, elem, stream);
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     switch (elem) {
         case GEN_F64: hipLaunchKernelGGL((gen_splitk_reduce_kernel<double, false>), grid, block, 0, stream, p); break;

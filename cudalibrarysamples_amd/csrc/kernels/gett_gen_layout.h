@@ -20,7 +20,7 @@ namespace ctamd {
 // not depend on which 16-row block of the tile it reads.
 template <int ES_, int BK_>
 struct GenImage {
-    static constexpr int ES  = ES_;           // element bytes: 2 (bf16 / fp16), 8 (fp64, complex64), 16 (complex128)
+    static constexpr int ES  = ES_;           // element bytes: 2 (bf16 / fp16), 4 (fp32), 8 (fp64, complex64), 16 (complex128)
     static constexpr int BK  = BK_;
     static constexpr int RB  = BK * ES;       // bytes per row
     static constexpr int UR  = RB / 16;       // 16-byte units per row
@@ -28,12 +28,12 @@ struct GenImage {
     static_assert(RB == 128 || RB == 64, "rows of 64 or 128 bytes");
     // Conflict-free for the fragment reads below on gfx950's ds_read_b128 lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...;
     // found by exhaustive search over the GF(2)-linear maps of the row's low four bits, tools/lds_swizzle_search.py):
-    //   128-byte rows, one unit per lane (16-bit):      unit ^ ((row >> 1) & 7)
+    //   128-byte rows, one unit per lane (16-bit, fp32): unit ^ ((row >> 1) & 7)
     //   128-byte rows, two units per lane (8 / 16-byte elements): unit ^ (((row >> 1) & 1) | (row & 4))
     //   64-byte rows (16-bit, BK = 32):                 unit ^ (((row >> 2) & 1) << 1)
     static CTAMD_HD int sw(int row) {
         if (RB == 64) return ((row >> 2) & 1) << 1;
-        return ES == 2 ? ((row >> 1) & 7) : (((row >> 1) & 1) | (row & 4));
+        return ES <= 4 ? ((row >> 1) & 7) : (((row >> 1) & 1) | (row & 4));
     }
     // byte address of element (row, k) of the tile
     static CTAMD_HD int addr(int row, int k) {
@@ -67,14 +67,15 @@ struct GenUnitMap {
 // MFMA fragment of a 16-row block for k-block s of the tile: lane (r = lane & 15, q = lane >> 4) reads UPL consecutive 16-byte
 // units, logical unit (4 s + q) * UPL + h, h < UPL, of row r.  The elements it gets are k = ((4 s + q) * UPL + h) * (16 / ES) + e.
 //   16-bit: UPL = 1 — 8 consecutive k for one v_mfma_f32_16x16x32_{bf16,f16} (A[i = r][k = 8 q + e], B likewise)
+//   fp32: UPL = 1 — 4 elements k = 4 q + j of k-block s (16 k); step j (v_mfma_f32_16x16x4_f32: A[i = r][k = q]) takes element j
 //   fp64 / complex64: UPL = 2 — 4 elements k = 4 q + j; step j of the k-block (v_mfma_*_16x16x4: A[i = r][k = q]) takes element j
 //   complex128: UPL = 2 — 2 elements k = 2 q + j
 // A and B use the same (q, j) -> k assignment, which is all the products need.
 template <int ES>
 struct GenFrag {
-    static constexpr int UPL = (ES == 2) ? 1 : 2;
+    static constexpr int UPL = (ES <= 4) ? 1 : 2;
     static constexpr int EPU = 16 / ES;                 // elements per 16-byte unit
-    static constexpr int KPB = 4 * UPL * EPU;           // k per k-block: 32 (16-bit), 16 (8-byte elements), 8 (complex128)
+    static constexpr int KPB = 4 * UPL * EPU;           // k per k-block: 32 (16-bit), 16 (fp32, 8-byte elements), 8 (complex128)
     static CTAMD_HD int unit(int s, int q, int h) { return (4 * s + q) * UPL + h; }
     static CTAMD_HD int k_of(int s, int q, int h, int e) { return unit(s, q, h) * EPU + e; }
 };

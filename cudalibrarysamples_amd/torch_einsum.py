@@ -16,7 +16,9 @@ _TORCH2CT = {torch.float32: ct.R_32F, torch.float64: ct.R_64F, torch.float16: ct
 # compute= of EinsumPlan / einsum (float32 tensors): index of the compute descriptor (CUTENSOR_COMPUTE_DESC_<name>).  A reduced-precision
 # name permits products of rounded operands — "16BF": bf16(a) * bf16(b); "16F": fp16(a) * fp16(b) (beyond +-65504: +-inf); "TF32": three
 # bf16 products of a hi / lo split (about 2^-16 relative per product) — always with fp32 accumulation; the planner may still answer in
-# full fp32.  "32F" (= None) is the default.
+# full fp32.  "32F" (= None) is the default.  On float64 / complex128 tensors the default is 64F, and "32F" is the reduced-precision
+# name: it permits products of operands rounded once to fp32 (complex: both parts) with fp32 accumulation — beyond 3.4e38: +-inf; the
+# planner may still answer in full fp64.
 _COMPUTE = {"16F": 0, "16BF": 1, "TF32": 2, "32F": 4}
 
 _handle = None
@@ -82,13 +84,14 @@ class EinsumPlan:
 
 
 def _check_compute(compute, dtype):
-    """None or one of _COMPUTE's names; anything but the default (None, "32F") needs float32 tensors.  Returns None for the default."""
+    """None or one of _COMPUTE's names.  "32F" SELECTS COMPUTE_DESC_32F on float64 / complex128 tensors and is the default everywhere
+    else; any other name needs float32 tensors.  Returns None for the default."""
     if compute is None:
         return None
     if compute not in _COMPUTE:
         raise ValueError("cutensor einsum: compute must be one of None, %s" % ", ".join(repr(k) for k in _COMPUTE))
     if compute == "32F":
-        return None
+        return compute if dtype in (torch.float64, torch.complex128) else None
     if dtype != torch.float32:
         raise ValueError("cutensor einsum: compute=%r needs float32 tensors, got %s" % (compute, dtype))
     return compute
@@ -100,8 +103,9 @@ _workspace = {}
 
 def einsum(equation, a, b=None, conj_a=False, conj_b=False, compute=None):
     """out = einsum(equation, a[, b]) on the GPU holding `a`.  Inputs must be contiguous.  conj_a / conj_b conjugate an
-    operand inside the contraction (python/cutensor/torch/einsum.py:50-61 uses them for complex gradients).  compute (float32
-    tensors only): None / "32F", or "TF32" / "16BF" / "16F" to permit reduced-precision products (see _COMPUTE)."""
+    operand inside the contraction (python/cutensor/torch/einsum.py:50-61 uses them for complex gradients).  compute: None (the
+    data type's default), on float32 tensors "TF32" / "16BF" / "16F", on float64 / complex128 tensors "32F", to permit
+    reduced-precision products (see _COMPUTE)."""
     compute = _check_compute(compute, a.dtype)
     if not a.is_cuda:
         raise RuntimeError("cutensor einsum runs on the GPU only (there is no CPU path)")
