@@ -160,7 +160,7 @@ bool plan_env_override() {
            CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_TRANSPOSE_T1") || CTAMD_HOOK_ENV("CUTENSOR_AMD_NT") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_SPLITK") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER") || CTAMD_HOOK_ENV("CUTENSOR_AMD_ABLATION") || CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") || CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X") ||
-           CTAMD_HOOK_ENV("CUTENSOR_AMD_F64X");
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_F64X") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32_SPLITK");
 }
 
 double scalar_as_double(const void* s, hipDataType t) {   // real part for complex scalar types
@@ -2066,6 +2066,7 @@ static hipError_t launch_tiled(const cutensorHandle_t handle, const cutensorPlan
     if (c.family == 0) {
         static const int policy = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_PARTIAL_STORE"); return e ? (e[0] == 'p' ? 1 : e[0] == 'n' ? 2 : e[0] == 's' ? 3 : 0) : 0; }();   // hooks flavour; 's': the row epilogue skips its stores (timing only)
         p.partialPolicy = policy;
+        p.noFlatStart = CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_FLAT_START", '0') ? 1 : 0;   // hooks flavour, read per call: a test runs both entries in one process
         if (plan.fusedFold) {
             uint32_t slot;
             {
@@ -2094,6 +2095,7 @@ static hipError_t launch_tiled(const cutensorHandle_t handle, const cutensorPlan
     r.partial = static_cast<float*>(workspace);
     r.C = p.C; r.D = p.D; r.alpha = p.alpha; r.beta = p.beta;
     r.alpha64 = s.a; r.beta64 = s.b; r.alphaIm = s.aIm; r.betaIm = s.bIm; r.conjC = p.conjC;
+    r.noFlatStart = p.noFlatStart;
     return launch_splitk_fold(c.family, tab[c.kernel], r, stream);
 }
 
@@ -2403,6 +2405,10 @@ int ctamdLastH16Kernel(void) try { return g_lastH16Kernel.load(std::memory_order
 void ctamdLaunchCounts(uint64_t out[5]) try {
     for (int i = 0; i < 5; ++i) out[i] = g_launchCounts[i].load(std::memory_order_relaxed);
 } CTAMD_API_CATCH_VOID
+
+// Launches of the fp32 ring kernels that took the flat entry (kernels/gett_f32_stream.hip, launch_stream) since the library was loaded:
+// tells a test which of the two entries its case ran on.
+uint64_t ctamdFlatStartCount(void) try { return g_flatStartLaunches.load(std::memory_order_relaxed); } CTAMD_API_CATCH_ZERO
 
 // Plan-memo counters of this handle: plans answered by cloning a prototype / plans that went through the planner.
 void ctamdPlanMemoStats(const cutensorHandle_t handle, uint64_t* hits, uint64_t* misses, uint32_t* entries) try {

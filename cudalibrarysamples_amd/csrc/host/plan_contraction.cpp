@@ -401,6 +401,10 @@ std::vector<ContractionChoice> rank_contraction_choices(const ContractionView& v
             if (tiles * s > (uint64_t)numCUs * 16) break;
             splits.push_back(s);
         }
+        if (const char* fs = CTAMD_HOOK_ENV("CUTENSOR_AMD_F32_SPLITK")) {   // tests: this many slices, also below four K-tiles per slice
+            const uint64_t want = std::strtoull(fs, nullptr, 10);
+            if (want >= 2 && want <= kTiles) splits = {(uint32_t)want};
+        }
         for (uint32_t s : splits) {
             ContractionChoice c;
             c.kernel = i;

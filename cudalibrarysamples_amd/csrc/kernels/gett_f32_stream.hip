@@ -35,6 +35,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "params.h"
 #include "launch.h"
 #include "gett_common.h"
@@ -127,6 +129,29 @@ struct StreamOperand {
                 uint32_t row = row0 + 4 * u;
                 if (row >= gFree.total) row = (gFree.total - 1u) & ~3u;   // the last unit that holds rows of the mode (whole when extent % 4 == 0)
                 src[i] = (group_offset32<0>(gFree, row) + (uint32_t)kr * (uint32_t)strideK0) * 4u;
+            }
+        }
+    }
+
+    // The flat entry's form (StreamFlatParams): the free group is ONE mode of `total` rows strideBytes apart; strideK0Bytes: byte stride of
+    // the fastest contracted mode.  Same units, same clamping as init().
+    __device__ __forceinline__ void init_flat(uint32_t strideBytes, uint32_t total, uint32_t strideK0Bytes, int wave, int lane) {
+#pragma unroll
+        for (int i = 0; i < PER_WAVE; ++i) {
+            const int c = wave + 4 * i;
+            if constexpr (LAY == LAY_K) {
+                const int r = 8 * c + (lane >> 3), p = lane & 7;
+                const int u = p ^ ((r >> 1) & 7);
+                uint32_t row = (uint32_t)r;
+                if (row >= total) row = total - 1;
+                src[i] = row * strideBytes + 16u * (uint32_t)u;
+            } else {
+                const int g = 64 * c + lane;
+                const int kr = g / UR, p = g % UR;
+                const int u = (p + 4 * ((kr >> 2) & 1)) % UR;
+                uint32_t row = 4u * (uint32_t)u;
+                if (row >= total) row = (total - 1u) & ~3u;
+                src[i] = row * strideBytes + (uint32_t)kr * strideK0Bytes;
             }
         }
     }
@@ -253,6 +278,51 @@ struct KOdometer {
             }
         }
     }
+    // The same walk from the flat entry's block (StreamFlatParams): 32-bit byte strides, and a decode is three divisions — the last
+    // digit is what remains.
+    __device__ static __forceinline__ uint32_t flat_div(const StreamFlatParams& f, int i, uint32_t n) {
+        return __umulhi(n, f.kMagic[i]) >> ((f.kShifts >> (8 * i)) & 0xffu);
+    }
+    // byte offsets of the digits above the second one, hi = their index
+    __device__ static __forceinline__ void flat_high(const StreamFlatParams& f, uint32_t hi, uint32_t& a, uint32_t& b) {
+        const uint32_t d3 = flat_div(f, 2, hi), d2 = hi - d3 * f.kExt[2];
+        a = d2 * f.kStrideA[2] + d3 * f.kStrideA[3];
+        b = d2 * f.kStrideB[2] + d3 * f.kStrideB[3];
+    }
+    __device__ __forceinline__ void init(const StreamFlatParams& f, uint32_t k0) {
+        const uint32_t E0 = f.kExt[0];                     // whole K-tiles (flat_start_params checks)
+        n0 = sgpr(E0 / kStreamBK);
+        e1 = sgpr(f.kExt[1]);
+        const uint32_t q0 = flat_div(f, 0, k0), d0 = k0 - q0 * E0;
+        j0 = sgpr(d0 / kStreamBK);
+        hi = sgpr((e1 < 2) ? q0 : flat_div(f, 1, q0));
+        j1 = sgpr(q0 - hi * e1);
+        uint32_t a, b;
+        flat_high(f, hi, a, b);
+        offA = sgpr(d0 * f.kStrideA[0] + j1 * f.kStrideA[1] + a);
+        offB = sgpr(d0 * f.kStrideB[0] + j1 * f.kStrideB[1] + b);
+        stepA = sgpr((uint32_t)kStreamBK * f.kStrideA[0]);
+        stepB = sgpr((uint32_t)kStreamBK * f.kStrideB[0]);
+        wrapA = sgpr(f.kStrideA[1] - (n0 - 1) * stepA);
+        wrapB = sgpr(f.kStrideB[1] - (n0 - 1) * stepB);
+    }
+    __device__ __forceinline__ void advance(const StreamFlatParams& f) {
+        const bool c0 = (j0 + 1 == n0);
+        j0 = c0 ? 0u : j0 + 1;
+        offA += c0 ? wrapA : stepA;
+        offB += c0 ? wrapB : stepB;
+        j1 += c0 ? 1u : 0u;
+        if (j1 == e1) {   // carry beyond the second digit
+            j1 = 0;
+            hi += 1;
+            if (hi * e1 * f.kExt[0] < f.kTotal) {
+                uint32_t a, b;
+                flat_high(f, hi, a, b);
+                offA = sgpr(a);
+                offB = sgpr(b);
+            }
+        }
+    }
 };
 
 template <int BM_, int BN_, int LA_, int LB_, int S_, int ABL_ = 0, bool RAG_ = false>
@@ -264,6 +334,11 @@ struct StreamCfg {
                                        // 3 = full kernel + wait-time accounting (slots 8-10 of the timing buffer),
                                        // 4 = full kernel (correct results), data movers at s_setprio 3
                                        // 5 = full kernel (correct results), operands streamed with the nontemporal policy
+                                       // 6 / 7 = the FLAT entry of 0 / 5 (StreamFlatParams: correct results, the same bits; launch_stream
+                                       // picks it).  Carried here and not in a parameter of its own: the instantiations' names are part of
+                                       // what the resource tests and the committed profiles match on
+    static constexpr bool FLAT = ABL_ == 6 || ABL_ == 7;
+    static constexpr bool NT = ABL_ == 5 || ABL_ == 7;
     static constexpr int TM = BM / 32, TN = BN / 32;    // 16 x 16 fragments per wave (2 x 2 waves)
 };
 
@@ -362,7 +437,7 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const GettParam
         int issued = 0;
         auto issue = [&](int slot) {
             float* stage = lds + slot * STAGE;
-            constexpr int AUX = (Cfg::ABL == 5) ? 2 : 0;       // 5 = correct results, nontemporal operand stream
+            constexpr int AUX = Cfg::NT ? 2 : 0;               // nontemporal operand stream
             if constexpr (Cfg::RAG) {
                 if (issued == maskAt) { oa.mask(wave, lane, kValid); ob.mask(wave, lane, kValid); }
                 ++issued;
@@ -382,176 +457,10 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const GettParam
                 }
             }
         };
-        if (tlog != nullptr && tid == 256) tlog[7] = __builtin_readcyclecounter();   // setup done, first issue
-        // Progressive start: the multiplying waves are released as soon as tile 0 has landed, while the
-        // rest of the ring is still being requested (an LDS-DMA issue that misses the TLB takes hundreds
-        // of cycles, so S tiles of issue time in front of barrier #0 would be S times the start-up cost).
-        issue(0);
-        if (nTiles > 1) {
-            issue(1);
-            CTAMD_WAIT_VMCNT(LOADS);
-        } else {
-            CTAMD_WAIT_VMCNT(0);
-            fix_last();                                    // ONE tile: it is the masked one
-        }
-        __builtin_amdgcn_s_barrier();                      // #0
-#pragma unroll
-        for (int T = 2; T < S; ++T)
-            if (T < nTiles) issue(T);
-        int slot = 0, t = 0;
-        unsigned long long waitV = 0, waitB = 0;
-        for (; t + S < nTiles; ++t) {                      // outstanding: tiles t+1 .. t+S-1
-            unsigned long long c0 = 0, c1 = 0, c2 = 0;
-            if constexpr (Cfg::ABL == 3) c0 = __builtin_readcyclecounter();
-            if constexpr (Cfg::ABL == 1) CTAMD_WAIT_VMCNT(0); else CTAMD_WAIT_VMCNT(LOADS * (S - 2));
-            if constexpr (Cfg::ABL == 3) c1 = __builtin_readcyclecounter();
-            __builtin_amdgcn_s_barrier();                  // #(t+1): slot t % S is free
-            if constexpr (Cfg::ABL == 3) { c2 = __builtin_readcyclecounter(); waitV += c1 - c0; waitB += c2 - c1; }
-            if constexpr (Cfg::ABL != 1) issue(slot);
-            slot = (slot + 1 == S) ? 0 : slot + 1;
-        }
-        if constexpr (Cfg::ABL == 3) {
-            if (tlog != nullptr && tid == 256) { tlog[9] = waitV; tlog[10] = waitB; }
-        }
-        // every tile is on its way: one barrier per remaining tile, waiting for exactly the tiles behind it
-        for (; t + 1 < nTiles; ++t) {
-            const int behind = nTiles - t - 2;             // tiles issued after tile t+1: 0 .. S-2
-            if (behind <= 0) { CTAMD_WAIT_VMCNT(0); fix_last(); }   // tile t + 1 is the last one
-            else if (behind == 1) CTAMD_WAIT_VMCNT(LOADS);
-            else if (behind == 2) CTAMD_WAIT_VMCNT(LOADS * 2);
-            else if (behind == 3) CTAMD_WAIT_VMCNT((S > 4 ? LOADS * 3 : 0));
-            else CTAMD_WAIT_VMCNT((S > 5 ? LOADS * 4 : 0));
-            __builtin_amdgcn_s_barrier();                  // #(t+1)
-        }
-        CTAMD_WAIT_VMCNT(0);
-        return;
+#include "gett_f32_stream_ring.inc"
     }
 
-    // =============================== multipliers ======================================================
-    __builtin_amdgcn_s_setprio(2);
-    const int wm = wave & 1, wn = wave >> 1;
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    int baseA[TM], baseB[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) baseA[i] = OpA::frag_base(wm * (BM / 2) + 16 * i, lane);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) baseB[j] = OpB::frag_base(wn * (BN / 2) + 16 * j, lane);
-
-    f32x4 a0[TM], b0[TN], a1[TM], b1[TN];   // fragments of the even / odd 16-step
-    auto load0 = [&](const float* st) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) a0[i] = OpA::template fragment<0>(st, baseA[i]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b0[j] = OpB::template fragment<0>(st + OpA::FLOATS, baseB[j]);
-    };
-    auto load1 = [&](const float* st) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) a1[i] = OpA::template fragment<1>(st, baseA[i]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b1[j] = OpB::template fragment<1>(st + OpA::FLOATS, baseB[j]);
-    };
-    // MFMAs [FIRST, LAST) of one 16-step, numbered kk-major so that consecutive MFMAs never share an
-    // accumulator (dependent latency 40 cycles > issue interval 32)
-#define CTAMD_MFMA_RANGE(FA, FB, FIRST, LAST)                                                          \
-    _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                     \
-    _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                   \
-        const int idx = (kk * TM + i) * TN + j;                                                        \
-        if (Cfg::ABL != 2 && idx >= (FIRST) && idx < (LAST))                                           \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(FA[i][kk], FB[j][kk], acc[i][j], 0, 0, 0); \
-    }
-    constexpr int NMFMA = 4 * TM * TN;          // MFMAs per 16-step
-    constexpr int SPLIT = NMFMA / 3;            // MFMAs of the odd step issued before the barrier
-    // scheduling hint: n x (1 MFMA, 1 LDS read)
-#define CTAMD_INTERLEAVE_DS(n)                                         \
-    _Pragma("unroll") for (int z = 0; z < (n); ++z) {                  \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             \
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             \
-    }
-
-    __builtin_amdgcn_s_barrier();                          // #0: tile 0 has landed
-    __builtin_amdgcn_sched_barrier(0);
-    load0(lds);
-    stamp(1);
-    unsigned long long waitC = 0;   // ABL == 3: cycles this wave spent in the per-tile barrier
-
-    // One K-tile in ring slot U (compile-time, so every LDS address is base + immediate).  The fragments
-    // of the odd 16-step are fetched under the MFMAs of the even step; the barrier sits a third into the
-    // odd step and the first fragments of the next tile are fetched under the remaining two thirds.
-#define CTAMD_TILE_BODY(U, LASTTILE) CTAMD_TILE_BODY_AT(lds + (U) * STAGE, lds + (((U) + 1) % S) * STAGE, LASTTILE)
-#define CTAMD_TILE_BODY_AT(CUR, NXT, LASTTILE) CTAMD_TILE_BODY_AT2(CUR, NXT, LASTTILE, load0, load1)
-#define CTAMD_TILE_BODY_AT2(CUR, NXT, LASTTILE, load0, load1)                                              \
-    {                                                                                                      \
-        const float* cur = (CUR);                                                                          \
-        const float* nxt = (NXT);                                                                          \
-        load1(cur);                                                                                        \
-        CTAMD_MFMA_RANGE(a0, b0, 0, NMFMA)                                                                 \
-        CTAMD_INTERLEAVE_DS(TM + 4 * TN)                                                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-        CTAMD_MFMA_RANGE(a1, b1, 0, SPLIT)                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-        if constexpr (!(LASTTILE)) {                                                                       \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* this wave's reads of the tile are back */ \
-            unsigned long long cb0 = 0;                                                                    \
-            if constexpr (Cfg::ABL == 3) cb0 = __builtin_readcyclecounter();                               \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            if constexpr (Cfg::ABL == 3) waitC += __builtin_readcyclecounter() - cb0;                      \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            load0(nxt);                                                                                    \
-            CTAMD_MFMA_RANGE(a1, b1, SPLIT, NMFMA)                                                         \
-            CTAMD_INTERLEAVE_DS(TM + 4 * TN)                                                               \
-        } else {                                                                                           \
-            CTAMD_MFMA_RANGE(a1, b1, SPLIT, NMFMA)                                                         \
-        }                                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-    }
-#define CTAMD_BODY_MID(U) CTAMD_TILE_BODY(U, false)
-    // compile-time unrolling over the ring slots
-#define CTAMD_FOR_SLOTS(M)                                                     \
-    { M(0) M(1) M(2)                                                           \
-      if constexpr (S > 3) { M(3) } if constexpr (S > 4) { M(4) }              \
-      if constexpr (S > 5) { M(5) } }
-    // whole ring turns whose S tiles all have a successor, then the last 1 .. S tiles (slots 0 .. r-1)
-    int t = 0;
-    for (; t + S < nTiles; t += S) CTAMD_FOR_SLOTS(CTAMD_BODY_MID)
-    stamp(2);
-    const int r = nTiles - t;
-#define CTAMD_BODY_END(U) CTAMD_TILE_BODY(U, (U) == S - 1)
-    if (r == S) {          // the common case (whole ring turns): straight-line code, no per-tile branch
-        CTAMD_FOR_SLOTS(CTAMD_BODY_END)
-    } else {
-        // 1 .. S - 1 tiles left (slots 0 .. r - 1): ONE rolled copy of the tile body with run-time slot addresses.  (Unrolled
-        // per slot with a branch on r in front of every copy, this tail alone spilled 90-180 VGPRs to scratch memory in the
-        // 128 x 128 instantiations — and a kernel that spills is one the next unrelated edit can break.)
-        // The fragment bases go through an opaque copy per use, so that derived addresses (base ^ 16, base + slot) are formed
-        // where they are needed instead of being carried through the loop in registers it does not have.
-        auto opaque = [](int v) { asm volatile("" : "+v"(v)); return v; };
-        auto load0t = [&](const float* st) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a0[i] = OpA::template fragment<0>(st, opaque(baseA[i]));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b0[j] = OpB::template fragment<0>(st + OpA::FLOATS, opaque(baseB[j]));
-        };
-        auto load1t = [&](const float* st) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a1[i] = OpA::template fragment<1>(st, opaque(baseA[i]));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b1[j] = OpB::template fragment<1>(st + OpA::FLOATS, opaque(baseB[j]));
-        };
-        int u = 0;
-#pragma unroll 1
-        for (; u + 1 < r; ++u) CTAMD_TILE_BODY_AT2(lds + u * STAGE, lds + (u + 1) * STAGE, false, load0t, load1t)
-        CTAMD_TILE_BODY_AT2(lds + u * STAGE, lds, true, load0t, load1t)     // u == r - 1
-    }
-    stamp(3);
-    if constexpr (Cfg::ABL == 3) {
-        if (tlog != nullptr && wave8 == 0 && lane_now() == 0) tlog[8] = waitC;
-    }
+#include "gett_f32_stream_kloop.inc"
 
     // ---- epilogue ------------------------------------------------------------------------------------
     // Everything the epilogue derives from the lane number is derived HERE (opaque copy): hoisted to kernel entry it would
@@ -761,6 +670,83 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const GettParam
     stamp(6);
 }
 
+// The FLAT entry of the same kernel (Cfg::FLAT; told apart by its argument block): one output tile, one M and one N mode, no batch, a
+// uniform split over whole K-tiles, partials only — the headline einsum.  Only what runs in front of the first LDS-DMA request / the
+// first barrier and the partial stores' address differ from the general entry: the arguments are two lines that arrive in one round
+// of scalar loads, the remapped workgroup id IS the slice, a row's offset is one multiply, and the odometer starts from three
+// divisions.  The ring schedule, the K loop and the bits of the partials are the general entry's (the two .inc files).
+template <class Cfg>
+__global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const StreamFlatParams p) {
+    static_assert(Cfg::FLAT && !Cfg::RAG, "the flat entry has no ragged form");
+    constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = kStreamBK, S = Cfg::S;
+    constexpr int TM = Cfg::TM, TN = Cfg::TN;
+    using OpA = StreamOperand<Cfg::LA, BM>;
+    using OpB = StreamOperand<Cfg::LB, BN>;
+    constexpr int STAGE = OpA::FLOATS + OpB::FLOATS;
+    constexpr int LOADS = OpA::PER_WAVE + OpB::PER_WAVE;
+    static_assert(S >= 3 && S <= 6 && S * STAGE * 4 <= 160 * 1024, "LDS ring must fit 160 KiB");
+    static_assert(LOADS * (S - 1) <= 63, "vmcnt is a 6-bit counter");
+    __shared__ __attribute__((aligned(16))) float lds[S * STAGE];
+
+    const int tid  = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = wave8 & 3;
+    const bool loader = wave8 >= 4;
+    unsigned long long* tlog = p.timing ? p.timing + (size_t)blockIdx.x * 16 : nullptr;
+    auto lane_now = []() -> int {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#else
+        return 0;
+#endif
+    };
+    auto stamp = [&](int slot) {   // the general entry's slots
+        if (tlog != nullptr && wave8 == 0 && lane_now() == 0) tlog[slot] = (slot >= 5 && slot != 7) ? wall_clock64() : __builtin_readcyclecounter();
+    };
+    stamp(0);
+    stamp(5);
+
+    const uint32_t slice = xcd_remap(blockIdx.x, p.nBlocks);
+    const uint32_t kBegin = slice * p.kPerSlice;
+    uint32_t kEnd = kBegin + p.kPerSlice;
+    if (kEnd > p.kTotal) kEnd = p.kTotal;
+    const int nTiles = (int)((kEnd - kBegin) / BK);         // any tile count >= 1
+
+    if (loader) {
+        const BufRsrc A = make_rsrc(p.A);
+        const BufRsrc B = make_rsrc(p.B);
+        OpA oa;
+        OpB ob;
+        oa.init_flat(p.sM, p.Mtot, p.kStrideA[0], wave, lane);
+        ob.init_flat(p.sN, p.Ntot, p.kStrideB[0], wave, lane);
+        KOdometer odo;
+        odo.init(p, kBegin);
+        auto issue = [&](int slot) {
+            float* stage = lds + slot * STAGE;
+            constexpr int AUX = Cfg::NT ? 2 : 0;
+            oa.template issue<AUX>(A, odo.offA, stage, wave);
+            ob.template issue<AUX>(B, odo.offB, stage + OpA::FLOATS, wave);
+            odo.advance(p);
+        };
+        auto fix_last = [] {};
+#include "gett_f32_stream_ring.inc"
+    }
+
+#include "gett_f32_stream_kloop.inc"
+
+    // accumulator-order partials, one tile image per slice: [slice][wave][i][j][lane] x 16 B, write-through as in the general entry
+    const int laneE = lane_now();
+    f32x4* P = reinterpret_cast<f32x4*>(p.partial) + ((size_t)slice * 4 + wave) * (size_t)(TM * TN * 64);
+    const BufRsrc rP = make_rsrc(reinterpret_cast<const float*>(P));
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) store_wt_16(acc[i][j], rP, (uint32_t)(((i * TN + j) * 64 + laneE) * 16));
+    stamp(4);
+    stamp(6);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Split-K fold for accumulator-order partials: D = alpha * sum_s partial[s] + beta * C.
 // One lane owns one 16-byte accumulator register quad (4 consecutive m at one n) of one output tile.
@@ -829,68 +815,91 @@ __global__ void __launch_bounds__(256) splitk_reduce_frag_kernel(const SplitKRed
 
 // The same fold for the common case of one M mode, one N mode and no batch: every argument fits one
 // 96-byte kernel-argument block, fetched in a single round (a dependent round of argument loads costs
-// ~0.45 us at the start of a 3-us kernel), and the output address is two multiplies.
+// ~0.45 us at the start of a 3-us kernel), and the output address is two multiplies.  The first 16 bytes
+// are all the partial loads need.
 struct FoldFlatParams {
     const float* partial;
-    const float* C;
+    uint32_t     splitK, quadsTotal;
     float*       D;
+    const float* C;
     int64_t      sDm, sDn, sCm, sCn;
     float        alpha, beta;
-    uint32_t     splitK, quadsTotal, fragTM, fragTN, tilesM, Mtot, Ntot;
+    uint32_t     tilesM, Mtot, Ntot;
+    uint32_t     fragTM, fragTN;     // read by the <NT, 0, 0> instantiation only
 };
 
 // NT threads = 8 quads x NT/8 slice groups; a lane keeps 256 / (NT/8) loads in flight per pass.
-template <int NT>
+// FTM x FTN: 16 x 16 fragments per wave of the GETT kernel that wrote the partials — the output decode divides by constants
+// (0, 0: read from the block).  Nothing between the kernel's entry and its partial loads depends on more than the first
+// argument round; the decode of e and the output addresses sit between the loads' issue and the first use of their data.
+template <int NT, int FTM, int FTN>
 __global__ void __launch_bounds__(NT) splitk_reduce_frag_flat_kernel(const FoldFlatParams p) {
     constexpr int G = NT / 8, U = 256 / G, W = NT / 64;
     __shared__ f32x4 red[W][8];
     const int q = threadIdx.x & 7, g = threadIdx.x >> 3;
     const uint32_t e = blockIdx.x * 8 + q;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    if (e < p.quadsTotal) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(p.partial) + e;
-        for (uint32_t s0 = g; s0 < p.splitK; s0 += 256) {
-            f32x4 x[U];
+    const bool live = e < p.quadsTotal;
+    const f32x4* src = reinterpret_cast<const f32x4*>(p.partial) + e;
+    auto load = [&](f32x4 (&x)[U], uint32_t s0) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t sl = s0 + (uint32_t)G * u;
-                x[u] = (sl < p.splitK) ? __builtin_nontemporal_load(src + (size_t)sl * p.quadsTotal) : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int st = 1; st < U; st <<= 1)
-#pragma unroll
-                for (int u = 0; u + st < U; u += 2 * st) x[u] += x[u + st];
-            sum += x[0];
+        for (int u = 0; u < U; ++u) {
+            const uint32_t sl = s0 + (uint32_t)G * u;
+            x[u] = (live && sl < p.splitK) ? __builtin_nontemporal_load(src + (size_t)sl * p.quadsTotal) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
+    };
+    auto tree = [](f32x4 (&x)[U]) {
+#pragma unroll
+        for (int st = 1; st < U; st <<= 1)
+#pragma unroll
+            for (int u = 0; u + st < U; u += 2 * st) x[u] += x[u + st];
+    };
+    f32x4 x[U];
+    load(x, (uint32_t)g);                                   // slices g, g + G, ..: the first (for splits up to 256, the only) pass
+    // decode e -> (nt, mt, wave, i, j, lane) and the addresses of the quad's four outputs, while the loads are in flight
+    const uint32_t fragTM = FTM ? (uint32_t)FTM : p.fragTM, fragTN = FTN ? (uint32_t)FTN : p.fragTN;
+    uint32_t rem = e;
+    const uint32_t lane = rem % 64; rem /= 64;
+    const uint32_t j = rem % fragTN; rem /= fragTN;
+    const uint32_t i = rem % fragTM; rem /= fragTM;
+    const uint32_t w = rem % 4; rem /= 4;
+    const uint32_t mt = (p.tilesM == 1u) ? 0u : rem % p.tilesM;
+    const uint32_t nt = (p.tilesM == 1u) ? rem : rem / p.tilesM;
+    const uint32_t bm = 32u * fragTM, bn = 32u * fragTN;
+    const uint32_t n = nt * bn + (w >> 1) * (bn / 2) + 16 * j + (lane & 15);
+    const uint32_t m0 = mt * bm + (w & 1) * (bm / 2) + 16 * i + 4 * (lane >> 4);
+    float* d = p.D + (int64_t)m0 * p.sDm + (int64_t)n * p.sDn;
+    const float* c = p.C + (int64_t)m0 * p.sCm + (int64_t)n * p.sCn;
+    tree(x);
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+    sum += x[0];
+    for (uint32_t s0 = g + 256u; s0 < p.splitK; s0 += 256) {
+        load(x, s0);
+        tree(x);
+        sum += x[0];
     }
 #pragma unroll
     for (int m = 8; m < 64; m <<= 1)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) sum[c] += __shfl_xor(sum[c], m, 64);
+        for (int cc = 0; cc < 4; ++cc) sum[cc] += __shfl_xor(sum[cc], m, 64);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) < 8) red[wave][q] = sum;
     __syncthreads();
-    if (threadIdx.x >= 8 || e >= p.quadsTotal) return;
+    if (threadIdx.x >= 8 || !live || n >= p.Ntot) return;
     sum = red[0][q];
 #pragma unroll
-    for (int w = 1; w < W; ++w) sum += red[w][q];
-    uint32_t rem = e;
-    const uint32_t lane = rem % 64; rem /= 64;
-    const uint32_t j = rem % p.fragTN; rem /= p.fragTN;
-    const uint32_t i = rem % p.fragTM; rem /= p.fragTM;
-    const uint32_t w = rem % 4; rem /= 4;
-    const uint32_t mt = rem % p.tilesM;
-    const uint32_t nt = rem / p.tilesM;
-    const uint32_t bm = 32u * p.fragTM, bn = 32u * p.fragTN;
-    const uint32_t n = nt * bn + (w >> 1) * (bn / 2) + 16 * j + (lane & 15);
-    if (n >= p.Ntot) return;
+    for (int ww = 1; ww < W; ++ww) sum += red[ww][q];
+    if (p.beta == 0.f) {               // no load of C
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (m0 + r < p.Mtot) d[r * p.sDm] = p.alpha * sum[r];
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const uint32_t m = mt * bm + (w & 1) * (bm / 2) + 16 * i + 4 * (lane >> 4) + r;
-        if (m >= p.Mtot) continue;
+        if (m0 + r >= p.Mtot) continue;
         float val = p.alpha * sum[r];
-        if (p.beta != 0.f) val += p.beta * p.C[(int64_t)m * p.sCm + (int64_t)n * p.sCn];
-        p.D[(int64_t)m * p.sDm + (int64_t)n * p.sDn] = val;
+        val += p.beta * c[r * p.sCm];
+        d[r * p.sDm] = val;
     }
 }
 
@@ -911,7 +920,12 @@ hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t st
         f.Mtot = p.gM.total; f.Ntot = p.gN.total;
         // 128 / 512 / 1024 threads per workgroup measured the same step time (43.6-44.0 us): the kernel is one memory
         // round trip plus launch, not throughput
-        hipLaunchKernelGGL(splitk_reduce_frag_flat_kernel<256>, dim3((unsigned)blocks), dim3(256), 0, stream, f);
+        const dim3 grid((unsigned)blocks), block(256);
+        const uint32_t frag = (p.noFlatStart == 0 && p.fragTM == p.fragTN) ? p.fragTM : 0u;   // the GETT tiles are 64, 96 or 128 square
+        if (frag == 2u) hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 2, 2>), grid, block, 0, stream, f);
+        else if (frag == 3u) hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 3, 3>), grid, block, 0, stream, f);
+        else if (frag == 4u) hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 4, 4>), grid, block, 0, stream, f);
+        else hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 0, 0>), grid, block, 0, stream, f);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(splitk_reduce_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
@@ -921,6 +935,37 @@ hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t st
 // ---------------------------------------------------------------------------------------------
 // Kernel table
 // ---------------------------------------------------------------------------------------------
+// launches that took the flat entry since the library was loaded (host/api.cpp: ctamdFlatStartCount)
+std::atomic<uint64_t> g_flatStartLaunches{0};
+
+// The flat entry's block, when the launch is one it covers: one output tile, one M and one N mode, no batch, a uniform split over whole
+// K-tiles whose partials (default store policy) are folded by a second kernel.  Strides go in as bytes modulo 2^32 — what the general
+// entry computes from the same 64-bit strides (the planner ranks these kernels for operands whose byte span fits 32 bits).
+static bool flat_start_params(const GettParams& p, StreamFlatParams& f) {
+    if (p.noFlatStart != 0 || p.partial == nullptr || p.sync != nullptr || p.xcdTiles != 0 || p.partialPolicy != 0) return false;
+    if (p.gL.total != 1 || p.gM.n > 1 || p.gN.n > 1 || p.tilesM * p.tilesN != 1 || p.nBlocks != p.splitK) return false;
+    if (p.gK.total % (uint32_t)kStreamBK != 0u || p.gK.div[0].d % (uint32_t)kStreamBK != 0u || (p.ragged & 1u) != 0u) return false;
+    f.A = static_cast<const float*>(p.A);
+    f.B = static_cast<const float*>(p.B);
+    f.partial = p.partial;
+    f.timing = p.timing;
+    f.sM = (uint32_t)p.gM.stride[0][0] * 4u; f.sN = (uint32_t)p.gN.stride[0][0] * 4u;
+    f.Mtot = p.gM.total; f.Ntot = p.gN.total;
+    f.splitK = p.splitK; f.kPerSlice = p.kPerSlice; f.nBlocks = p.nBlocks;
+    f.kTotal = p.gK.total;
+    f.kShifts = 0;
+    for (int i = 0; i < kMaxGroupModes; ++i) {
+        f.kExt[i] = p.gK.div[i].d;
+        f.kStrideA[i] = (uint32_t)p.gK.stride[0][i] * 4u;
+        f.kStrideB[i] = (uint32_t)p.gK.stride[1][i] * 4u;
+        if (i < kMaxGroupModes - 1) {
+            f.kMagic[i] = p.gK.div[i].magic;
+            f.kShifts |= (p.gK.div[i].shift & 0xffu) << (8 * i);
+        }
+    }
+    return true;
+}
+
 template <class Cfg>
 static hipError_t launch_stream(const GettParams& p, hipStream_t stream) {
     if constexpr (Cfg::ABL == 0) {
@@ -929,6 +974,16 @@ static hipError_t launch_stream(const GettParams& p, hipStream_t stream) {
         if (p.gK.total % (uint32_t)kStreamBK != 0u || (p.ragged & 1u) != 0u) {
             using R = StreamCfg<Cfg::BM, Cfg::BN, Cfg::LA, Cfg::LB, 4, 0, true>;
             hipLaunchKernelGGL(gett_f32_stream_kernel<R>, dim3(p.nBlocks), dim3(512), 0, stream, p);
+            return hipGetLastError();
+        }
+    }
+    // the kernels the planner ranks for one-tile split-K plans (96 x 96 on the 3-deep ring, default and nontemporal stream) have a flat twin
+    if constexpr (Cfg::BM == 96 && Cfg::BN == 96 && Cfg::S == 3 && (Cfg::ABL == 0 || Cfg::ABL == 5)) {
+        StreamFlatParams f;
+        if (flat_start_params(p, f)) {
+            using F = StreamCfg<96, 96, Cfg::LA, Cfg::LB, 3, Cfg::ABL == 0 ? 6 : 7>;
+            hipLaunchKernelGGL(gett_f32_stream_kernel<F>, dim3(p.nBlocks), dim3(512), 0, stream, f);
+            g_flatStartLaunches.fetch_add(1, std::memory_order_relaxed);
             return hipGetLastError();
         }
     }

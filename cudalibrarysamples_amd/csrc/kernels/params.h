@@ -74,7 +74,35 @@ struct GettParams {
     // tilesM2 x tilesN2 tiles from (mOrg2, nOrg2); tilesM2 * tilesN2 == 0: none.  The two edge strips of an output (rows past the
     // interior, columns past the interior) are ONE launch that way.
     uint32_t    tilesM2, tilesN2, mOrg2, nOrg2;
+    // test switch (CUTENSOR_AMD_FLAT_START=0, hooks flavour): the streaming fp32 kernels and their fold take the general entry also where
+    // the flat one applies (gett_f32_stream.hip, StreamFlatParams).  (Four bytes of the struct's tail padding: the block keeps its size.)
+    int32_t     noFlatStart;
 };
+
+// ---------------------------------------------------------------------------------------------
+// The streaming fp32 kernels' FLAT entry (gett_f32_stream.hip): one output tile, one M mode, one N mode, no batch, a uniform split-K
+// whose partials are folded by a second kernel — the headline einsum's case.  Everything the kernel needs before its first memory
+// request fits two 64-byte lines, arrives in one round of scalar loads and is used as it stands: no tile decode, no mixed-radix
+// decode of the rows, and C, D, the scalars and every output stride are not arguments at all.  Byte strides are modulo 2^32, as the
+// general entry computes them (operand byte spans fit 32 bits).
+// ---------------------------------------------------------------------------------------------
+struct StreamFlatParams {
+    const float* A;
+    const float* B;
+    float*       partial;           // accumulator-order partials, one tile image per slice
+    unsigned long long* timing;     // diagnostics (GettParams::timing)
+    uint32_t     sM, sN;            // byte stride of the M mode in A / of the N mode in B
+    uint32_t     Mtot, Ntot;
+    uint32_t     splitK, kPerSlice, nBlocks;   // nBlocks == splitK
+    uint32_t     kTotal;
+    // the K group: extents, the magic numbers of the three divisions a decode needs (the last digit is what remains), their shifts
+    // (byte i = shift of digit i), byte strides in A and B
+    uint32_t     kExt[kMaxGroupModes];
+    uint32_t     kMagic[kMaxGroupModes - 1];
+    uint32_t     kShifts;
+    uint32_t     kStrideA[kMaxGroupModes], kStrideB[kMaxGroupModes];
+};
+static_assert(sizeof(StreamFlatParams) == 128, "the flat entry's arguments are two 64-byte lines");
 
 // ---------------------------------------------------------------------------------------------
 // Contractions with more unfusable modes per group than kMaxGroupModes (e.g. the 25-mode extent-2 tensors of
@@ -120,6 +148,7 @@ struct SplitKReduceParams {
     // double2), scalars at full width, conjugation of C
     double       alpha64, beta64, alphaIm, betaIm;
     int32_t      conjC;
+    int32_t      noFlatStart;    // GettParams::noFlatStart (tail padding: the block keeps its size)
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -114,6 +114,8 @@ lib.ctamdPlanMemoStats.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.
 lib.ctamdPlanMemoStats.restype = None
 lib.ctamdLaunchCounts.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
 lib.ctamdLaunchCounts.restype = None
+lib.ctamdFlatStartCount.argtypes = []
+lib.ctamdFlatStartCount.restype = ctypes.c_uint64
 lib.ctamdLastH16Kernel.argtypes = []
 lib.ctamdLastH16Kernel.restype = ctypes.c_int
 lib.ctamdSetTimingBuffer.argtypes = [_vp, _vp]
@@ -158,6 +160,12 @@ def launch_counts():
     out = (ctypes.c_uint64 * 5)()
     lib.ctamdLaunchCounts(out)
     return dict(zip(("simple", "wide", "f32", "h16", "gen"), [int(v) for v in out]))
+
+
+def flat_start_count():
+    """Launches of the fp32 ring kernels that took their flat entry (one output tile, flat M / N, no batch, split-K with a separate fold)
+    since the library was loaded."""
+    return int(lib.ctamdFlatStartCount())
 
 
 def last_h16_kernel():
