@@ -414,52 +414,73 @@ static double f64_direct_estimate_us(const ContractionView& v, const Contraction
 // set while the inner contraction of a repacked plan is estimated / planned: the temporaries are final, no second round of copies
 static thread_local bool t_inRepack = false;
 
-// ---- reduced-precision compute descriptors on fp32 data (kernels/gett_gen_f32x.inc) -------------------------------------------
-// COMPUTE_DESC_16F / _16BF / _TF32 on a contraction whose tensors are all real fp32 with fp32 scalars PERMIT products of rounded
-// operands (fp16, bf16, three bf16 products of a hi / lo split); the fp32 kernels stay a legal answer.  Returns the general family's
-// element for the descriptor, or -1 when the contraction is not of that kind.
+// ---- reduced-precision compute descriptors on fp32 and complex64 data (kernels/gett_gen_f32x.inc, gett_gen_c32x.inc) ------------
+// COMPUTE_DESC_16F / _16BF / _TF32 on a contraction whose tensors are all real fp32 with fp32 scalars — or all complex64 with
+// complex-float scalars — PERMIT products of rounded operands (fp16, bf16, three bf16 products of a hi / lo split; complex: each of the
+// four real products of a complex one); the fp32 / complex64 kernels stay a legal answer.  Returns the general family's element for the
+// descriptor, or -1 when the contraction is not of that kind.
 static int f32x_elem_of(const cutensorOperationDescriptor& d) {
-    if (d.kind != OpKind::Contraction || d.compute == nullptr || d.scalarType != HIP_R_32F) return -1;
+    if (d.kind != OpKind::Contraction || d.compute == nullptr || (d.scalarType != HIP_R_32F && d.scalarType != HIP_C_32F)) return -1;
     for (const TensorUse* t : {&d.A, &d.B, &d.C, &d.D})
-        if (t->present && t->desc.dtype != HIP_R_32F) return -1;
+        if (t->present && t->desc.dtype != d.scalarType) return -1;
+    const bool cplx = d.scalarType == HIP_C_32F;
     switch (d.compute->id) {
-        case 0:  return GEN_F32_F16;
-        case 1:  return GEN_F32_BF16;
-        case 2:  return GEN_F32_BF16X3;
+        case 0:  return cplx ? GEN_C32_F16 : GEN_F32_F16;
+        case 1:  return cplx ? GEN_C32_BF16 : GEN_F32_BF16;
+        case 2:  return cplx ? GEN_C32_BF16X3 : GEN_F32_BF16X3;
         default: return -1;
     }
+}
+static const char* f32x_desc_name(int elem) {
+    return (elem == GEN_F32_F16 || elem == GEN_C32_F16) ? "16F" : (elem == GEN_F32_BF16 || elem == GEN_C32_BF16) ? "16BF" : "TF32";
 }
 // CUTENSOR_AMD_F32X (test-hooks flavour): "force" — the reduced-precision kernels whenever the descriptor permits them; "0" — never
 static int f32x_switch() {
     const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X");
     return (e == nullptr) ? 0 : (e[0] == 'f') ? 1 : (e[0] == '0') ? -1 : 0;
 }
-// Whether a plan for view `v` (fp32 data, descriptor element `elem`) takes the reduced-precision kernels: `g` is their choice, `ch32` the
-// ranked fp32 candidates (best first).  By the model, only problems it can place: 16-byte loads on both operands, no split-K (the
-// headline einsum's class stays on the fp32 split-K kernels), at least one workgroup per CU, and an estimate clearly below the fp32
-// plan's.  `note` says which side won and on what numbers (the CUTENSOR_LOG_LEVEL plan line).
+// Whether a plan for view `v` (fp32 or complex64 data, descriptor element `elem`) takes the reduced-precision kernels: `g` is their
+// choice.  The full-precision side is `ch32`, the ranked fp32 candidates (best first), for fp32 data; for complex64 data (`ch32` is not
+// read) it is the complex64 plan pick_gen_choice gives the same view, at its measured rate — both sides from
+// gen_c32_measured_estimate_us (plan_contraction.cpp): one formula.  ONE rule for both: by the model, only problems it can place —
+// 16-byte loads on both operands, no split-K on either side (the headline einsum's class stays on the split-K kernels), at least one
+// output tile per CU, and an estimate below 0.8 x the full-precision plan's.  `note` says which side won and on what numbers (the
+// CUTENSOR_LOG_LEVEL plan line).
 static bool f32x_decide(const ContractionView& v, int elem, uint64_t wsLimit, int numCUs, bool explicitPick,
                         const std::vector<ContractionChoice>& ch32, ContractionChoice& g, std::string& note) {
     const int sw = f32x_switch();
     char buf[256];
     if (elem < 0 || v.wide || explicitPick || t_inRepack || sw < 0) return false;
-    if (!pick_gen_choice(v, wsLimit, numCUs, g, elem)) { note = "no reduced-precision kernel for this view -> fp32 kernels"; return false; }
-    const double t32 = (!ch32.empty() && ch32[0].family == 0 && ch32[0].kernel >= 0) ? ch32[0].estimateUs : -1.0;
+    const bool cplx = gen_elem_is_c32x(elem);
+    const char* full = cplx ? "complex64" : "fp32";
+    if (!pick_gen_choice(v, wsLimit, numCUs, g, elem)) {
+        note = std::string("no reduced-precision kernel for this view -> ") + full + " kernels";
+        return false;
+    }
+    double t32 = -1.0;
+    uint32_t split32 = 1;
+    if (cplx) {
+        ContractionChoice g32;
+        if (pick_gen_choice(v, wsLimit, numCUs, g32)) { t32 = gen_c32_measured_estimate_us(v, g32, numCUs); split32 = g32.splitK; }
+    } else if (!ch32.empty() && ch32[0].family == 0 && ch32[0].kernel >= 0) {
+        t32 = ch32[0].estimateUs;
+        split32 = ch32[0].splitK;
+    }
     if (sw > 0) {
-        std::snprintf(buf, sizeof buf, "reduced-precision kernels forced (model %.1f us, fp32 plan %.1f us)", g.estimateUs, t32);
+        std::snprintf(buf, sizeof buf, "reduced-precision kernels forced (model %.1f us, %s plan %.1f us)", g.estimateUs, full, t32);
         note = buf;
         return true;
     }
     const GettKernelInfo& k = *kernel_info(2, g.kernel);
     const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
     const char* why = nullptr;
-    if (t32 < 0.0) why = "no fp32 MFMA plan to compare with";
-    else if (k.vec != 4) why = "element gathers";
-    else if (g.splitK > 1 || ch32[0].splitK > 1) why = "split-K problem";
+    if (t32 < 0.0) why = "no full-precision MFMA plan to compare with";
+    else if (k.vec != (cplx ? 2 : 4)) why = "element gathers";
+    else if (g.splitK > 1 || split32 > 1) why = "split-K problem";
     else if (tiles < (double)numCUs) why = "fewer output tiles than CUs";
     else if (!(g.estimateUs < 0.8 * t32)) why = "model sees no gain";
-    std::snprintf(buf, sizeof buf, "%s (model: reduced-precision %.1f us, fp32 plan %.1f us)%s%s", why ? "fp32 kernels kept" : "reduced-precision kernels",
-                  g.estimateUs, t32, why ? ": " : "", why ? why : "");
+    std::snprintf(buf, sizeof buf, "%s %s (model: reduced-precision %.1f us, %s plan %.1f us)%s%s", why ? full : "reduced-precision", why ? "kernels kept" : "kernels",
+                  g.estimateUs, full, t32, why ? ": " : "", why ? why : "");
     note = buf;
     return why == nullptr;
 }
@@ -1183,6 +1204,12 @@ static cutensorStatus_t estimate_contraction(const cutensorHandle_t handle, cute
             *estimate = gc.workspace;
             return CUTENSOR_STATUS_SUCCESS;
         }
+        // a reduced-precision compute descriptor on complex64 data: likewise — the float2 partials of that kernel
+        if (v.dtype == HIP_C_32F && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0') &&
+            f32x_decide(v, f32x_elem_of(desc), cap, numCUs, planPref != nullptr && names_candidate_or_tunes(*planPref), {}, gc, note)) {
+            *estimate = gc.workspace;
+            return CUTENSOR_STATUS_SUCCESS;
+        }
         if (!pick_gen_choice(v, cap, numCUs, gc)) return CUTENSOR_STATUS_SUCCESS;
         *estimate = gc.workspace;
         // fp64 on element gathers: an operand copied first when that pays (plan_repack)
@@ -1623,7 +1650,7 @@ static TiledRoute rank_tiled_candidates(const PlanRequest& rq, const cutensorPla
             r.ch.assign(1, gx);
             r.tDirectUs = 0.0;
         }
-        if (xe >= 0 && !note.empty()) CT_LOG("plan: fp32 contraction, compute descriptor %s: %s", xe == GEN_F32_F16 ? "16F" : xe == GEN_F32_BF16 ? "16BF" : "TF32", note.c_str());
+        if (xe >= 0 && !note.empty()) CT_LOG("plan: fp32 contraction, compute descriptor %s: %s", f32x_desc_name(xe), note.c_str());
     }
     if (r.genPath && !r.h16Path) {
         // COMPUTE_DESC_32F on fp64 / complex128 data: the fp32-rate kernels when the model (or CUTENSOR_AMD_F64X=force) says so.  They take
@@ -1634,6 +1661,12 @@ static TiledRoute rank_tiled_candidates(const PlanRequest& rq, const cutensorPla
         if (xe >= 0 && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0') && f64x_decide(v, xe, rq.wsLimit, numCUs, names_candidate_or_tunes(rq.pr), gx, note))
             r.ch.assign(1, gx);
         if (xe >= 0 && !note.empty()) CT_LOG("plan: %s contraction, compute descriptor 32F: %s", xe == GEN_F64_F32 ? "fp64" : "complex128", note.c_str());
+        // a reduced-precision compute descriptor on complex64 data (16BF / 16F / TF32): the 16-bit-rate kernels when the model (or
+        // CUTENSOR_AMD_F32X=force) says so, on the operands as they lie; a caller who names a candidate gets the complex64 plan as ever
+        const int ce = (v.dtype == HIP_C_32F && !CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0')) ? f32x_elem_of(desc) : -1;
+        std::string cnote;
+        if (ce >= 0 && f32x_decide(v, ce, rq.wsLimit, numCUs, names_candidate_or_tunes(rq.pr), r.ch, gx, cnote)) r.ch.assign(1, gx);
+        if (ce >= 0 && !cnote.empty()) CT_LOG("plan: complex64 contraction, compute descriptor %s: %s", f32x_desc_name(ce), cnote.c_str());
         if (!r.ch.empty()) return r;
     }
     if ((v.dtype == HIP_R_64F || v.dtype == HIP_C_32F) && desc.scalarType == v.dtype && r.genPath && r.ch.empty()) {   // fp64 / complex64 on element gathers (plan_repack)

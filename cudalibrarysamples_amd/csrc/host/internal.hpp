@@ -141,6 +141,9 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
 // what f64x_decide compares: an fp64 / complex128 plan of the general family, or its single-precision twin, at its measured rate
 double gen_f64_measured_estimate_us(const ContractionView& v, const ContractionChoice& c, int numCUs);
 // (or fp64 / complex128 data under COMPUTE_DESC_32F — GEN_F64_F32 / GEN_C64_C32, gett_gen_f64x.inc)
+// what f32x_decide compares on complex64 data: a complex64 plan of the general family, or its reduced-precision twin, at its measured rate
+double gen_c32_measured_estimate_us(const ContractionView& v, const ContractionChoice& c, int numCUs);
+// (or complex64 data under COMPUTE_DESC_16BF / _16F / _TF32 — GEN_C32_BF16 / GEN_C32_F16 / GEN_C32_BF16X3, gett_gen_c32x.inc)
 bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c, int f32xElem = -1);
 // 16-bit family: the default kernel variant first, then the other variants of the same tile / split (the candidates
 // CUTENSOR_ALGO_DEFAULT_PATIENT and incremental autotuning measure)

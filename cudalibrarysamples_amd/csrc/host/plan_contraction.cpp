@@ -715,7 +715,8 @@ std::vector<ContractionChoice> rank_h16_choices(const ContractionView& v, uint64
 // when the fastest free mode is) and the widest unit V its extents, strides and pointer alignment admit; the kernel runs both
 // operands at the smaller V.  Tile: the large one when it still fills the chip.  Split-K for every element type when the output
 // tiles alone leave most CUs idle: partials in the accumulator type — fp32 for 16-bit data (folded by launch_splitk_reduce with one
-// rounding), double / float2 / double2 otherwise (launch_gen_splitk_reduce).
+// rounding), double / float2 / double2 otherwise (launch_gen_splitk_reduce).  Under a reduced-precision compute descriptor fp32 and
+// complex64 data take the 16-bit-rate kernels of gett_gen_f32x.inc / gett_gen_c32x.inc when the caller names their element.
 // ---------------------------------------------------------------------------------------------
 // efficiency of the reduced-precision fp32 kernels against their MFMA ceiling (one product per k-block / three): see pick_gen_choice
 static constexpr double kF32xEffX1 = 0.18, kF32xEffX3 = 0.275;
@@ -726,6 +727,12 @@ static constexpr double kF64xEffReal = 0.66, kF64xEffCplx = 0.67;
 // ... and what the fp64 kernels of this family sustain of THEIR MFMA rate where they stage 16-byte units: 60-63 of 78.6 TFLOP/s at fp64
 // 4096^3, 62 at complex128 2048^3
 static constexpr double kF64GenEff = 0.78;
+// complex64 data: what gett_gen_kernel<GEN_C32> sustains of the 157.3 TFLOP/s of v_mfma_f32_16x16x4_f32 where it stages 16-byte units, and
+// what the reduced-precision complex64 kernels (gett_gen_c32x.inc) sustain of the 16-bit MFMA rate (2516.6 TFLOP/s; a third of it for the
+// three products of TF32), on 8 real flops per complex multiply-add: fitted to the 32F and the forced-path rows of the 2048^3 and 4096^3
+// layouts in profiles/c32x_compute.jsonl — complex64 120-131 TFLOP/s, forced 16BF / 16F 499-628, forced TF32
+// 269-290: see gen_c32_measured_estimate_us
+static constexpr double kC32GenEff = 0.80, kC32xEffX1 = 0.22, kC32xEffX3 = 0.33;
 
 static int gen_elem_of(hipDataType t) {
     switch (t) {
@@ -765,10 +772,11 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     // fp64 / complex128 data takes the single-precision-compute kernels when the caller names their element (GEN_F64_F32 / GEN_C64_C32)
     const int elem = (v.dtype == HIP_R_32F) ? (gen_elem_is_f32x(f32xElem) ? f32xElem : -1)
                    : (v.dtype == HIP_R_64F && f32xElem == GEN_F64_F32) || (v.dtype == HIP_C_64F && f32xElem == GEN_C64_C32) ? f32xElem
+                   : (v.dtype == HIP_C_32F && gen_elem_is_c32x(f32xElem)) ? f32xElem      // complex64 data under 16BF / 16F / TF32 (gett_gen_c32x.inc)
                    : gen_elem_of(v.dtype);
     if (elem < 0 || v.wide) return false;
-    const bool f32x = gen_elem_is_f32x(elem), f64x = gen_elem_is_f64x(elem);
-    const int maxV = (elem == GEN_C64 || elem == GEN_C64_C32) ? 1 : (elem == GEN_F64 || elem == GEN_C32 || elem == GEN_F64_F32) ? 2 : f32x ? 4 : 8;
+    const bool f32x = gen_elem_is_f32x(elem), f64x = gen_elem_is_f64x(elem), c32x = gen_elem_is_c32x(elem);
+    const int maxV = (elem == GEN_C64 || elem == GEN_C64_C32) ? 1 : (elem == GEN_F64 || elem == GEN_C32 || elem == GEN_F64_F32 || c32x) ? 2 : f32x ? 4 : 8;
     int orient[2], vec[2];
     for (int o = 0; o < 2; ++o) {
         const bool slotA = o == 0;
@@ -828,8 +836,9 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     c.kPerSlice = (uint32_t)(tilesPerSlice * k.bk);
     c.workspace = (c.splitK > 1) ? (uint64_t)c.splitK * perSliceBytes : 0ull;
     // rough time: the family's MFMA rate for the type at ~50 % utilisation (only used for logs / describe)
-    const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32 || f64x) ? 256.0 : f32x ? (elem == GEN_F32_BF16X3 ? 4096.0 / 3.0 : 4096.0) : 128.0;
-    const double flops = ((elem == GEN_C32 || elem == GEN_C64 || elem == GEN_C64_C32) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
+    const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32 || f64x) ? 256.0 : f32x ? (elem == GEN_F32_BF16X3 ? 4096.0 / 3.0 : 4096.0)
+                              : c32x ? (elem == GEN_C32_BF16X3 ? 4096.0 / 3.0 : 4096.0) : 128.0;
+    const double flops = ((elem == GEN_C32 || elem == GEN_C64 || elem == GEN_C64_C32 || c32x) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
     c.estimateUs = std::ceil(tiles * c.splitK / (double)numCUs) * flops / (flopPerClkCU * 2.4e9 * 0.5) * 1e6 + 2.0;
     if (f32x) {
         // The estimate that decides between these kernels and the ranked fp32 candidates (cutensorCreatePlan).  Waves of workgroups at
@@ -843,6 +852,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         c.estimateUs = std::max(tCompute, bytes / 4.0e12 * 1e6) + 4.0;
     }
     if (f64x) c.estimateUs = gen_f64_measured_estimate_us(v, c, numCUs);
+    if (c32x) c.estimateUs = gen_c32_measured_estimate_us(v, c, numCUs);
     return true;
 }
 
@@ -865,6 +875,26 @@ double gen_f64_measured_estimate_us(const ContractionView& v, const ContractionC
     const double flops = (cplx ? 8.0 : 2.0) * k.bm * k.bn * (double)(c.kPerSlice ? c.kPerSlice : v.totK);
     const double tCompute = std::ceil(tiles * std::max<uint32_t>(c.splitK, 1u) / (double)numCUs) * flops / rate * 1e6;
     const double bytes = (double)dtype_size(v.dtype) * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
+    return std::max(tCompute, bytes / 4.0e12 * 1e6) + 2.0;
+}
+
+// The same for complex64 data: what f32x_decide (api.cpp) compares a complex64 plan of this family (gett_gen_kernel<GEN_C32>) with its
+// reduced-precision twin (gett_gen_c32x_kernel) on.  ONE formula for both sides, each at its measured rate: 8 real flops per complex
+// multiply-add on the fp32 MFMA x kC32GenEff, or on the 16-bit MFMA (a third of it under TF32) x kC32xEffX1 / kC32xEffX3; never below what
+// moving the operands and the output once at 4 TB/s costs; + 2 us for the launch.  Negative: `c` is not such a plan.
+double gen_c32_measured_estimate_us(const ContractionView& v, const ContractionChoice& c, int numCUs) {
+    int count = 0;
+    const GettKernelInfo* tab = gett_gen_kernels(&count);
+    if (c.family != 2 || c.kernel < 0 || c.kernel >= count) return -1.0;
+    const GettKernelInfo& k = tab[c.kernel];
+    const bool c32x = gen_elem_is_c32x(k.elem);
+    if (!c32x && k.elem != GEN_C32) return -1.0;
+    const double perClk = !c32x ? 256.0 * kC32GenEff : k.elem == GEN_C32_BF16X3 ? 4096.0 / 3.0 * kC32xEffX3 : 4096.0 * kC32xEffX1;
+    const double rate = perClk * 2.4e9;      // flop / s / CU
+    const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
+    const double flops = 8.0 * k.bm * k.bn * (double)(c.kPerSlice ? c.kPerSlice : v.totK);
+    const double tCompute = std::ceil(tiles * std::max<uint32_t>(c.splitK, 1u) / (double)numCUs) * flops / rate * 1e6;
+    const double bytes = 8.0 * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
     return std::max(tCompute, bytes / 4.0e12 * 1e6) + 2.0;
 }
 

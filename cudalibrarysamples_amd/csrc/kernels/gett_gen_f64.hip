@@ -69,6 +69,7 @@ hipError_t launch_gen_splitk_reduce(const SplitKReduceParams& p, int elem, hipSt
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     switch (elem) {
         case GEN_F64: hipLaunchKernelGGL((gen_splitk_reduce_kernel<double, false>), grid, block, 0, stream, p); break;
+        case GEN_C32_BF16: case GEN_C32_F16: case GEN_C32_BF16X3:      // (complex64 data, float2 partials: gett_gen_c32x.inc)
         case GEN_C32: hipLaunchKernelGGL((gen_splitk_reduce_kernel<float, true>), grid, block, 0, stream, p); break;
         case GEN_C64: hipLaunchKernelGGL((gen_splitk_reduce_kernel<double, true>), grid, block, 0, stream, p); break;
         default: return hipErrorInvalidValue;

@@ -57,9 +57,14 @@ enum GenElem : int { GEN_BF16 = 0, GEN_F16 = 1, GEN_F64 = 2, GEN_C32 = 3, GEN_C6
                      GEN_F32_BF16 = 5, GEN_F32_F16 = 6, GEN_F32_BF16X3 = 7,
                      // fp64 / complex128 DATA under COMPUTE_DESC_32F (gett_gen_f64x.inc): operands rounded to fp32 / complex64 on their way
                      // into LDS, fp32 MFMA and accumulators, fp32 / float2 partials, fp64 epilogue and fold
-                     GEN_F64_F32 = 8, GEN_C64_C32 = 9 };
+                     GEN_F64_F32 = 8, GEN_C64_C32 = 9,
+                     // complex64 DATA under a reduced-precision compute descriptor (gett_gen_c32x.inc): real and imaginary parts rounded to
+                     // bf16 / fp16, or split into two bf16 planes each (COMPUTE_DESC_TF32), on their way into LDS; four (twelve) 16-bit MFMAs per
+                     // complex product; fp32 accumulators, float2 partials and the complex64 epilogue and fold of GEN_C32
+                     GEN_C32_BF16 = 10, GEN_C32_F16 = 11, GEN_C32_BF16X3 = 12 };
 inline bool gen_elem_is_f32x(int elem) { return elem >= GEN_F32_BF16 && elem <= GEN_F32_BF16X3; }
 inline bool gen_elem_is_f64x(int elem) { return elem == GEN_F64_F32 || elem == GEN_C64_C32; }
+inline bool gen_elem_is_c32x(int elem) { return elem >= GEN_C32_BF16 && elem <= GEN_C32_BF16X3; }
 // split-K partials of the element type are fp32 rows folded by launch_splitk_reduce (else: launch_gen_splitk_reduce — the fp32 / float2
 // partials of the gen_elem_is_f64x elements among them, whose fold is in fp64)
 inline bool gen_elem_f32_partials(int elem) { return elem == GEN_BF16 || elem == GEN_F16 || gen_elem_is_f32x(elem); }
@@ -84,15 +89,17 @@ const GettKernelInfo* gett_h16p_kernels(int* count);   // gett_h16p.hip (persist
 // general MFMA family: bf16 / fp16 shapes the aligned kernels above refuse (no 16-byte lanes, K not in whole 64-deep tiles), fp64,
 // complex64 / complex128 — register-staged, any strides and extents (gett_gen.inc; the table is the concatenation of the three
 // translation units gett_gen_h16.hip / gett_gen_f64.hip / gett_gen_cplx.hip, then — appended, so that every earlier index stays — the
-// reduced-precision fp32 kernels of gett_gen_f32x.hip, then the single-precision-compute fp64 / complex128 kernels of gett_gen_f64x.hip)
+// reduced-precision fp32 kernels of gett_gen_f32x.hip, then the single-precision-compute fp64 / complex128 kernels of gett_gen_f64x.hip,
+// then the reduced-precision complex64 kernels of gett_gen_c32x.hip)
 const GettKernelInfo* gett_gen_kernels(int* count);
 const GettKernelInfo* gett_gen_h16_kernels(int* count);
 const GettKernelInfo* gett_gen_f64_kernels(int* count);
 const GettKernelInfo* gett_gen_cplx_kernels(int* count);
 const GettKernelInfo* gett_gen_f32x_kernels(int* count);
 const GettKernelInfo* gett_gen_f64x_kernels(int* count);
+const GettKernelInfo* gett_gen_c32x_kernels(int* count);
 // split-K fold of the general family's fp64 / complex kernels: D = alpha * sum_s partial[s] + beta * op(C); partials
-// [slice][L][M][N] in the accumulator type of `elem` (GEN_F64: double, GEN_C32: float2, GEN_C64: double2; GEN_F64_F32: float and
+// [slice][L][M][N] in the accumulator type of `elem` (GEN_F64: double, GEN_C32 and GEN_C32_BF16 / _F16 / _BF16X3: float2, GEN_C64: double2; GEN_F64_F32: float and
 // GEN_C64_C32: float2, summed and scaled in fp64 on fp64 C / D — gett_gen_f64x.hip)
 hipError_t launch_gen_splitk_reduce(const SplitKReduceParams& p, int elem, hipStream_t stream);
 hipError_t launch_gen_f64x_splitk_reduce(const SplitKReduceParams& p, int elem, hipStream_t stream);

@@ -18,7 +18,8 @@ _TORCH2CT = {torch.float32: ct.R_32F, torch.float64: ct.R_64F, torch.float16: ct
 # bf16 products of a hi / lo split (about 2^-16 relative per product) — always with fp32 accumulation; the planner may still answer in
 # full fp32.  "32F" (= None) is the default.  On float64 / complex128 tensors the default is 64F, and "32F" is the reduced-precision
 # name: it permits products of operands rounded once to fp32 (complex: both parts) with fp32 accumulation — beyond 3.4e38: +-inf; the
-# planner may still answer in full fp64.
+# planner may still answer in full fp64.  On complex64 tensors "16BF" / "16F" / "TF32" permit the same products for each of the four real
+# products of a complex one (fp32 accumulation and complex epilogue); the planner may still answer with the complex64 kernels.
 _COMPUTE = {"16F": 0, "16BF": 1, "TF32": 2, "32F": 4}
 
 _handle = None
@@ -85,15 +86,15 @@ class EinsumPlan:
 
 def _check_compute(compute, dtype):
     """None or one of _COMPUTE's names.  "32F" SELECTS COMPUTE_DESC_32F on float64 / complex128 tensors and is the default everywhere
-    else; any other name needs float32 tensors.  Returns None for the default."""
+    else; any other name needs float32 or complex64 tensors.  Returns None for the default."""
     if compute is None:
         return None
     if compute not in _COMPUTE:
         raise ValueError("cutensor einsum: compute must be one of None, %s" % ", ".join(repr(k) for k in _COMPUTE))
     if compute == "32F":
         return compute if dtype in (torch.float64, torch.complex128) else None
-    if dtype != torch.float32:
-        raise ValueError("cutensor einsum: compute=%r needs float32 tensors, got %s" % (compute, dtype))
+    if dtype not in (torch.float32, torch.complex64):
+        raise ValueError("cutensor einsum: compute=%r needs float32 or complex64 tensors, got %s" % (compute, dtype))
     return compute
 
 
@@ -104,7 +105,7 @@ _workspace = {}
 def einsum(equation, a, b=None, conj_a=False, conj_b=False, compute=None):
     """out = einsum(equation, a[, b]) on the GPU holding `a`.  Inputs must be contiguous.  conj_a / conj_b conjugate an
     operand inside the contraction (python/cutensor/torch/einsum.py:50-61 uses them for complex gradients).  compute: None (the
-    data type's default), on float32 tensors "TF32" / "16BF" / "16F", on float64 / complex128 tensors "32F", to permit
+    data type's default), on float32 / complex64 tensors "TF32" / "16BF" / "16F", on float64 / complex128 tensors "32F", to permit
     reduced-precision products (see _COMPUTE)."""
     compute = _check_compute(compute, a.dtype)
     if not a.is_cuda:
