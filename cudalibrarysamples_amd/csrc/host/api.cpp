@@ -926,9 +926,19 @@ cutensorStatus_t cutensorCreateContractionTrinary(const cutensorHandle_t handle,
         s1.scalarType = s2.scalarType = op.scalarType;
         s1.A = X; s1.B = Y; s1.C = T; s1.D = T;
         s2.A = T; s2.B = Z; s2.C = op.D; s2.D = op.E;
-        ContractionView v1, v2;
-        std::string why;
-        if (build_contraction_view(s1, v1, &why) != CUTENSOR_STATUS_SUCCESS || build_contraction_view(s2, v2, &why) != CUTENSOR_STATUS_SUCCESS) continue;
+        // a step is validated the way cutensorCreateContraction validates it: a mode that one of its inputs alone carries (a mode of A, B
+        // or C that E lacks) makes it the reduction(s) + the contraction on the temporaries (split_lone_modes), as its plan will be
+        auto step_ok = [&](const cutensorOperationDescriptor& s) {
+            ContractionView v;
+            std::string why;
+            TwoStepSplit ls;
+            if (!split_lone_modes(s, ls)) return build_contraction_view(s, v, &why) == CUTENSOR_STATUS_SUCCESS;
+            ReducePlan rp;
+            if (ls.hasA && plan_reduction(ls.stepA, 0, handle->numCUs, rp, &why) != CUTENSOR_STATUS_SUCCESS) return false;
+            if (ls.hasB && plan_reduction(ls.stepB, 0, handle->numCUs, rp, &why) != CUTENSOR_STATUS_SUCCESS) return false;
+            return build_contraction_view(ls.inner, v, &why) == CUTENSOR_STATUS_SUCCESS;
+        };
+        if (!step_ok(s1) || !step_ok(s2)) continue;
         s1.flops = flops1; s2.flops = flops2;
         const double cost = flops1 + flops2 + 8.0 * tElems;   // the intermediate is written and read once
         if (!found || cost < bestCost) {
@@ -2466,9 +2476,21 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     if (plan == nullptr || buf == nullptr || len == 0) return -1;
     int n = 0;
     if (plan->kind == OpKind::BlockSparseContraction) return blocksparse_describe(*plan, buf, len);
-    if (plan->kind == OpKind::ContractionTrinary)
-        return std::snprintf(buf, len, "{\"op\":\"contraction_trinary\",\"intermediate_bytes\":%llu,\"workspace\":%llu}",
-                             (unsigned long long)plan->tBytes, (unsigned long long)plan->requiredWorkspace);
+    if (plan->kind == OpKind::ContractionTrinary) {
+        // "order": the inputs (0 = A, 1 = B, 2 = C) as the two steps take them — X and Y contracted first, then Z; the two pairwise plans' own descriptions
+        n = std::snprintf(buf, len, "{\"op\":\"contraction_trinary\",\"intermediate_bytes\":%llu,\"workspace\":%llu,\"order\":[%d,%d,%d]",
+                          (unsigned long long)plan->tBytes, (unsigned long long)plan->requiredWorkspace, plan->triOrder[0], plan->triOrder[1], plan->triOrder[2]);
+        for (int i = 0; i < 2; ++i) {
+            if (n < 0 || (size_t)n >= len) return -1;
+            n += std::snprintf(buf + n, len - (size_t)n, ",\"step%d\":", i + 1);
+            if ((size_t)n >= len) return -1;
+            const cutensorPlan_t step = i == 0 ? plan->sub1.get() : plan->sub2.get();
+            const int m = step ? ctamdDescribePlan(step, buf + n, len - (size_t)n) : -1;
+            if (m < 0 || (size_t)(n + m) >= len) return -1;
+            n += m;
+        }
+        return n + std::snprintf(buf + n, len - (size_t)n, "}");
+    }
     if (plan->kind == OpKind::Contraction && plan->planKind == PlanKind::Peeled && plan->sub1) {
         // peeled contraction: the inner (tiled) plan's description with the peel in front (and how many peeled modes are contracted ones)
         long long launches = 1;
@@ -2547,6 +2569,10 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
         // a converting plan (kernels/elementwise_convert.hip): the hipDataType values of A and of D
         if (e.converts() && n > 1 && (size_t)n < len && buf[n - 1] == '}')
             n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"convert\":[%d,%d]}", (int)e.dtypeA, (int)e.dtypeD);
+        // a padded permutation: the elements the fill writes (the whole padded buffer) and the element offset of the interior, beside the inner plan's fields
+        if (plan->kind == OpKind::Permutation && plan->padFillElems != 0 && n > 1 && (size_t)n < len && buf[n - 1] == '}')
+            n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"pad\":[%llu,%lld]}", (unsigned long long)plan->padFillElems,
+                                      (long long)plan->padOffsetElems);
     }
     return n;
 } CTAMD_API_CATCH_INT

@@ -24,6 +24,8 @@
 
 using namespace ctamd;
 
+extern "C" int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len);   // api.cpp
+
 struct cutensorBlockSparseTensorDescriptor {
     uint32_t numModes = 0;
     uint64_t nnz = 0;
@@ -211,8 +213,21 @@ cutensorStatus_t blocksparse_plan(cutensorHandle_t handle, const cutensorOperati
 
 int blocksparse_describe(const cutensorPlan& pl, char* buf, size_t len) {
     if (!pl.bsp) return -1;
-    return std::snprintf(buf, len, "{\"op\":\"blocksparse\",\"tasks\":%zu,\"dense_plans\":%zu,\"workspace\":%llu}", pl.bsp->tasks.size(),
-                         pl.bsp->plans.size(), (unsigned long long)pl.requiredWorkspace);
+    // "scale_plans": the identity permutations of the output blocks no pair contributes to; "kernels": the distinct kernels of the dense plans
+    std::vector<std::string> names;
+    for (cutensorPlan_t p : pl.bsp->plans) {
+        char one[2048];
+        if (ctamdDescribePlan(p, one, sizeof one) <= 0) continue;
+        const std::string d(one), key("\"kname\":\"");
+        const size_t at = d.rfind(key);             // (a two-step dense plan: the inner contraction's name comes last)
+        if (at == std::string::npos) continue;
+        const std::string name = d.substr(at + key.size(), d.find('"', at + key.size()) - at - key.size());
+        if (std::find(names.begin(), names.end(), name) == names.end()) names.push_back(name);
+    }
+    std::string list;
+    for (const std::string& s : names) list += (list.empty() ? "\"" : ",\"") + s + "\"";
+    return std::snprintf(buf, len, "{\"op\":\"blocksparse\",\"tasks\":%zu,\"dense_plans\":%zu,\"workspace\":%llu,\"scale_plans\":%zu,\"kernels\":[%s]}",
+                         pl.bsp->tasks.size(), pl.bsp->plans.size(), (unsigned long long)pl.requiredWorkspace, pl.bsp->scalePlans.size(), list.c_str());
 }
 
 }  // namespace ctamd

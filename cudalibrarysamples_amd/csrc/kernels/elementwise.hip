@@ -338,16 +338,23 @@ static hipError_t launch_wide_ew(const Ew2DParams& p, int variant, bool un, unsi
     return hipGetLastError();
 }
 
-// Contiguous fill with 16-byte stores (HBM-bound: n * sizeof(T) bytes written).
+// Contiguous fill with 16-byte stores (HBM-bound: n * sizeof(T) bytes written).  The base needs the element's alignment only: the bytes
+// up to the first 16-byte boundary (head) and those behind the last whole lane (tail) are written one per thread.  The pattern's period
+// is the element size, which divides 16 and the head's length, so head, body and tail all index it from byte 0.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct FillPattern { uint32_t w[4]; };
 
-__global__ void __launch_bounds__(256) ew_fill_kernel(u32x4* D16, uint64_t n16, unsigned char* tail, uint32_t tailBytes, FillPattern pat) {
+__global__ void __launch_bounds__(256) ew_fill_kernel(u32x4* D16, uint64_t n16, unsigned char* head, uint32_t headBytes, unsigned char* tail,
+                                                      uint32_t tailBytes, FillPattern pat) {
     const u32x4 v = {pat.w[0], pat.w[1], pat.w[2], pat.w[3]};
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride)
         __builtin_nontemporal_store(v, D16 + i);
-    if (blockIdx.x == 0 && threadIdx.x < tailBytes) tail[threadIdx.x] = (unsigned char)(pat.w[(threadIdx.x >> 2) & 3] >> (8 * (threadIdx.x & 3)));
+    if (blockIdx.x == 0) {
+        const unsigned char b = (unsigned char)(pat.w[(threadIdx.x >> 2) & 3] >> (8 * (threadIdx.x & 3)));
+        if (threadIdx.x < headBytes) head[threadIdx.x] = b;
+        if (threadIdx.x < tailBytes) tail[threadIdx.x] = b;
+    }
 }
 
 static uint16_t fill_f32_to_bf16(float f) {
@@ -378,14 +385,18 @@ hipError_t launch_fill(void* D, uint64_t n, int dtype, double value, hipStream_t
         case HIP_C_64F: { uint64_t u; std::memcpy(&u, &value, 8); pat = FillPattern{{(uint32_t)u, (uint32_t)(u >> 32), 0u, 0u}}; es = 16; break; }
         default: return hipErrorInvalidValue;
     }
-    if ((reinterpret_cast<uintptr_t>(D) & 15) != 0) return hipErrorInvalidValue;   // descriptors carry >= 16-byte alignment here
-    const uint64_t bytes = n * es, n16 = bytes / 16;
-    const uint32_t tailBytes = (uint32_t)(bytes % 16);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(D);
+    if (base % es != 0) return hipErrorInvalidValue;   // (a padded permutation's output, a block of a block-sparse D: the element's alignment)
+    const uint64_t bytes = n * es;
+    const uint32_t headBytes = (uint32_t)std::min<uint64_t>(bytes, (16 - (base & 15)) & 15);
+    const uint64_t n16 = (bytes - headBytes) / 16;
+    const uint32_t tailBytes = (uint32_t)((bytes - headBytes) % 16);
     uint64_t blocks = (n16 + 255) / 256;
     if (blocks > 256u * 32u) blocks = 256u * 32u;
     if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(ew_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<u32x4*>(D), n16,
-                       static_cast<unsigned char*>(D) + n16 * 16, tailBytes, pat);
+    unsigned char* body = static_cast<unsigned char*>(D) + headBytes;
+    hipLaunchKernelGGL(ew_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<u32x4*>(body), n16,
+                       static_cast<unsigned char*>(D), headBytes, body + n16 * 16, tailBytes, pat);
     return hipGetLastError();
 }
 

@@ -195,8 +195,8 @@ def getErrorString(status):
 
 
 def describe_plan(plan):
-    buf = ctypes.create_string_buffer(1024)
-    lib.ctamdDescribePlan(plan, buf, 1024)
+    buf = ctypes.create_string_buffer(4096)
+    lib.ctamdDescribePlan(plan, buf, 4096)
     import json
     return json.loads(buf.value.decode())
 

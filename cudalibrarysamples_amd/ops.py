@@ -202,8 +202,10 @@ def permutation_plan(handle, extA, modesA, extB, modesB, dtype=ct.R_32F, strideA
         r = (ctypes.c_int32 * n)(*right)
         ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 4, l, 4 * n))    # PADDING_LEFT
         ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 5, r, 4 * n))    # PADDING_RIGHT
-        v = _typed_value(value, dtypeB) if dtypeB != dtype else (ctypes.c_double(value) if dtype == ct.R_64F else ctypes.c_float(value))
-        ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 6, ctypes.byref(v), ctypes.sizeof(v)))   # PADDING_VALUE
+        if value is not None:          # (None: the descriptor's default, zero)
+            # bytes: the value as the caller laid it out, passed through as it is; else one real value in the output's storage format
+            v = (ctypes.c_char * len(value)).from_buffer_copy(value) if isinstance(value, (bytes, bytearray)) else _typed_value(value, dtypeB)
+            ct.check(ct.cutensorOperationDescriptorSetAttribute(handle.h, op, 6, ctypes.byref(v), ctypes.sizeof(v)))   # PADDING_VALUE
     plan_kw.setdefault("workspace_limit", 0)   # elementwise_permute.cu:183-187
     return Plan(handle, op, "permutation", dtype, **plan_kw)
 
@@ -245,15 +247,41 @@ def trinary_plan(handle, extA, modesA, extB, modesB, extC, modesC, extD, modesD,
 
 
 def contraction_trinary_plan(handle, extA, modesA, extB, modesB, extC, modesC, extD, modesD, dtype=ct.R_32F, compute=None,
-                             alignment=128, **plan_kw):
-    """E = alpha * A * B * C + beta * D — cutensorCreateContractionTrinary (contraction_trinary.cu:191-198); E shares
-    D's descriptor as in the sample."""
-    dA, dB, dC, dD = _desc3(handle, [(extA, None), (extB, None), (extC, None), (extD, None)], dtype, alignment)
+                             alignment=128, strideA=None, strideB=None, strideC=None, strideD=None, strideE=None, opA=ct.OP_IDENTITY,
+                             opB=ct.OP_IDENTITY, opC=ct.OP_IDENTITY, opD=ct.OP_IDENTITY, **plan_kw):
+    """E = alpha * opA(A) * opB(B) * opC(C) + beta * opD(D) — cutensorCreateContractionTrinary (contraction_trinary.cu:191-198); E shares
+    D's descriptor as in the sample unless strideE gives it pitches of its own (same extents and modes)."""
+    dA, dB, dC, dD = _desc3(handle, [(extA, strideA), (extB, strideB), (extC, strideC), (extD, strideD)], dtype, alignment)
+    dE = tensor_descriptor(handle, extD, strideE, dtype, alignment) if strideE is not None else dD
     opd = ctypes.c_void_p()
-    st = ct.cutensorCreateContractionTrinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), ct.OP_IDENTITY, dB, ct.i32(modesB),
-                                             ct.OP_IDENTITY, dC, ct.i32(modesC), ct.OP_IDENTITY, dD, ct.i32(modesD), ct.OP_IDENTITY,
-                                             dD, ct.i32(modesD), ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
-    for d in (dA, dB, dC, dD):
+    st = ct.cutensorCreateContractionTrinary(handle.h, ctypes.byref(opd), dA, ct.i32(modesA), _unary(opA), dB, ct.i32(modesB),
+                                             _unary(opB), dC, ct.i32(modesC), _unary(opC), dD, ct.i32(modesD), _unary(opD),
+                                             dE, ct.i32(modesD), ct.compute_desc(compute or _DTYPE_COMPUTE[dtype]))
+    for d in {id(x): x for x in (dA, dB, dC, dD, dE)}.values():
         ct.cutensorDestroyTensorDescriptor(d)
     ct.check(st)
     return Plan(handle, opd, "contraction_trinary", dtype, **plan_kw)
+
+
+def blocksparse_plan(handle, sections, modes, blocks, dtype=ct.R_64F, compute=None, strides=(None, None, None), **plan_kw):
+    """D = alpha * A * B + beta * C over blocks — cutensorCreateBlockSparseTensorDescriptor / cutensorCreateBlockSparseContraction
+    (blocksparse.cu:102-107, :177-182).  sections: mode -> the extents of its sections; modes = (modesA, modesB, modesC); blocks = per
+    tensor the section coordinates of its stored blocks; strides: per tensor None (packed blocks) or one stride list per block.  C and D
+    share one descriptor as in the sample."""
+    descs = []
+    for m, coords, st in zip(modes, blocks, strides):
+        d = ctypes.c_void_p()
+        ct.check(ct.cutensorCreateBlockSparseTensorDescriptor(
+            handle.h, ctypes.byref(d), len(m), len(coords), (ctypes.c_uint32 * len(m))(*[len(sections[c]) for c in m]),
+            ct.i64([e for c in m for e in sections[c]]), ct.i32([x for c in coords for x in c]),
+            ct.i64([x for blk in st for x in blk]) if st is not None else None, dtype))
+        descs.append(d)
+    op = ctypes.c_void_p()
+    mA, mB, mC = modes
+    st = ct.cutensorCreateBlockSparseContraction(handle.h, ctypes.byref(op), descs[0], ct.i32(mA), ct.OP_IDENTITY, descs[1], ct.i32(mB),
+                                                 ct.OP_IDENTITY, descs[2], ct.i32(mC), ct.OP_IDENTITY, descs[2], ct.i32(mC),
+                                                 ct.compute_desc(compute or ("64F" if dtype == ct.R_64F else "32F")))
+    for d in descs:
+        ct.cutensorDestroyBlockSparseTensorDescriptor(d)
+    ct.check(st)
+    return Plan(handle, op, "blocksparse", dtype, **plan_kw)

@@ -218,22 +218,7 @@ def hook_env(case):
 
 
 def _blocksparse_plan(ct, ops, h, case, dt, plan_kw):
-    descs = []
-    for m, coords in zip(case.modes, case.blocks):
-        d = ctypes.c_void_p()
-        ct.check(ct.cutensorCreateBlockSparseTensorDescriptor(
-            h.h, ctypes.byref(d), len(m), len(coords), (ctypes.c_uint32 * len(m))(*[len(case.ext[c]) for c in m]),
-            ct.i64([e for c in m for e in case.ext[c]]), ct.i32([x for c in coords for x in c]), None, dt))
-        descs.append(d)
-    op = ctypes.c_void_p()
-    mA, mB, mC = case.modes
-    st = ct.cutensorCreateBlockSparseContraction(h.h, ctypes.byref(op), descs[0], ct.i32(mA), ct.OP_IDENTITY, descs[1], ct.i32(mB),
-                                                 ct.OP_IDENTITY, descs[2], ct.i32(mC), ct.OP_IDENTITY, descs[2], ct.i32(mC),
-                                                 ct.compute_desc("64F" if case.dtype == "float64" else "32F"))
-    for d in descs:
-        ct.cutensorDestroyBlockSparseTensorDescriptor(d)
-    ct.check(st)
-    return ops.Plan(h, op, "blocksparse", dt, **plan_kw)
+    return ops.blocksparse_plan(h, case.ext, case.modes, case.blocks, dtype=dt, **plan_kw)
 
 
 def make_plan(ct, ops, h, case, **plan_kw):
