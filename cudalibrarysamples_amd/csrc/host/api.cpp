@@ -2109,7 +2109,11 @@ static hipError_t launch_tiled(const cutensorHandle_t handle, const cutensorPlan
     if (c.family == 0) {
         static const int policy = [] { const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_PARTIAL_STORE"); return e ? (e[0] == 'p' ? 1 : e[0] == 'n' ? 2 : e[0] == 's' ? 3 : 0) : 0; }();   // hooks flavour; 's': the row epilogue skips its stores (timing only)
         p.partialPolicy = policy;
-        p.noFlatStart = CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_FLAT_START", '0') ? 1 : 0;   // hooks flavour, read per call: a test runs both entries in one process
+        {   // hooks flavour, read per call: a test runs every entry in one process
+            const char* e = CTAMD_HOOK_ENV("CUTENSOR_AMD_FLAT_START");
+            p.noFlatStart = (e == nullptr) ? FLAT_START_ARGS : e[0] == '0' ? FLAT_START_GENERAL : e[0] == '2' ? FLAT_START_STRUCT
+                            : e[0] == '3' ? FLAT_START_ARGS_FOLD : e[0] == '4' ? FLAT_START_ARGS_GETT : FLAT_START_ARGS;
+        }
         if (plan.fusedFold) {
             uint32_t slot;
             {

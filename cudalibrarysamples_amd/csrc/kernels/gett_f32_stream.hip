@@ -45,6 +45,12 @@ namespace ctamd {
 
 constexpr int kStreamBK = 32;
 
+// measurement: -DCTAMD_FLAT_STRAIGHT_TAIL=0 builds the flat entries with the rolled K-loop tail of the general entry
+// (gett_f32_stream_kloop.inc), to price the straight-line tail on its own
+#ifndef CTAMD_FLAT_STRAIGHT_TAIL
+#define CTAMD_FLAT_STRAIGHT_TAIL 1
+#endif
+
 // 64 lanes x 16 B into one contiguous 1-KiB piece of LDS starting at the wave-uniform address dst (the
 // compiler moves it to M0).  Source = buffer descriptor (SGPRs) + per-lane byte offset (a loop-invariant
 // VGPR) + wave-uniform byte offset of the K-tile (an SGPR): `buffer_load_dwordx4 v, s[0:3], s offen lds`.
@@ -337,8 +343,10 @@ struct StreamCfg {
                                        // 6 / 7 = the FLAT entry of 0 / 5 (StreamFlatParams: correct results, the same bits; launch_stream
                                        // picks it).  Carried here and not in a parameter of its own: the instantiations' names are part of
                                        // what the resource tests and the committed profiles match on
-    static constexpr bool FLAT = ABL_ == 6 || ABL_ == 7;
-    static constexpr bool NT = ABL_ == 5 || ABL_ == 7;
+                                       // 8 / 9 = the flat entry of 0 / 5 on SCALAR kernel parameters, whose leading ones are preloaded
+                                       // into SGPRs (the same body, the same bits as 6 / 7)
+    static constexpr bool FLAT = ABL_ >= 6 && ABL_ <= 9;
+    static constexpr bool NT = ABL_ == 5 || ABL_ == 7 || ABL_ == 9;
     static constexpr int TM = BM / 32, TN = BN / 32;    // 16 x 16 fragments per wave (2 x 2 waves)
 };
 
@@ -676,7 +684,14 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const GettParam
 // of scalar loads, the remapped workgroup id IS the slice, a row's offset is one multiply, and the odometer starts from three
 // divisions.  The ring schedule, the K loop and the bits of the partials are the general entry's (the two .inc files).
 template <class Cfg>
-__global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const StreamFlatParams p) {
+struct StreamFlatRing {
+    static constexpr int STAGE = StreamOperand<Cfg::LA, Cfg::BM>::FLOATS + StreamOperand<Cfg::LB, Cfg::BN>::FLOATS;
+    static constexpr int FLOATS = Cfg::S * STAGE;
+};
+
+// the body of both flat entries: `lds` is the entry's ring (StreamFlatRing<Cfg>::FLOATS floats)
+template <class Cfg>
+__device__ __forceinline__ void gett_f32_stream_flat_body(const StreamFlatParams& p, float* lds) {
     static_assert(Cfg::FLAT && !Cfg::RAG, "the flat entry has no ragged form");
     constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = kStreamBK, S = Cfg::S;
     constexpr int TM = Cfg::TM, TN = Cfg::TN;
@@ -686,7 +701,6 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const StreamFla
     constexpr int LOADS = OpA::PER_WAVE + OpB::PER_WAVE;
     static_assert(S >= 3 && S <= 6 && S * STAGE * 4 <= 160 * 1024, "LDS ring must fit 160 KiB");
     static_assert(LOADS * (S - 1) <= 63, "vmcnt is a 6-bit counter");
-    __shared__ __attribute__((aligned(16))) float lds[S * STAGE];
 
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
@@ -720,14 +734,34 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const StreamFla
         OpB ob;
         oa.init_flat(p.sM, p.Mtot, p.kStrideA[0], wave, lane);
         ob.init_flat(p.sN, p.Ntot, p.kStrideB[0], wave, lane);
+        // Scalar parameters: the per-lane offsets above need preloaded SGPRs only, the odometer needs the K group, which one round of
+        // scalar loads fetches (StreamFlatTail).  Left to the scheduler, the odometer's scalar work moves up front and the wave waits
+        // for that round first; passing the K group through an empty asm that also takes the offsets keeps its first use — and so
+        // the wait — behind the vector work, which then covers the round.
+        StreamFlatParams f = p;
+        if constexpr (Cfg::ABL >= 8) {
+            uint32_t done = 0;
+#pragma unroll
+            for (int i = 0; i < OpA::PER_WAVE; ++i) done |= oa.src[i];
+#pragma unroll
+            for (int i = 0; i < OpB::PER_WAVE; ++i) done |= ob.src[i];
+            auto behind = [&](uint32_t& v) { asm volatile("" : "+s"(v) : "v"(done)); };
+#pragma unroll
+            for (int i = 0; i < kMaxGroupModes; ++i) {
+                behind(f.kExt[i]);
+                if (i > 0) { behind(f.kStrideA[i]); behind(f.kStrideB[i]); }
+                if (i < kMaxGroupModes - 1) behind(f.kMagic[i]);
+            }
+            behind(f.kShifts);
+        }
         KOdometer odo;
-        odo.init(p, kBegin);
+        odo.init(f, kBegin);
         auto issue = [&](int slot) {
             float* stage = lds + slot * STAGE;
             constexpr int AUX = Cfg::NT ? 2 : 0;
             oa.template issue<AUX>(A, odo.offA, stage, wave);
             ob.template issue<AUX>(B, odo.offB, stage + OpA::FLOATS, wave);
-            odo.advance(p);
+            odo.advance(f);
         };
         auto fix_last = [] {};
 #include "gett_f32_stream_ring.inc"
@@ -745,6 +779,38 @@ __global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const StreamFla
         for (int j = 0; j < TN; ++j) store_wt_16(acc[i][j], rP, (uint32_t)(((i * TN + j) * 64 + laneE) * 16));
     stamp(4);
     stamp(6);
+}
+
+template <class Cfg>
+__global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const StreamFlatParams p) {
+    __shared__ __attribute__((aligned(16))) float lds[StreamFlatRing<Cfg>::FLOATS];
+    gett_f32_stream_flat_body<Cfg>(p, lds);
+}
+
+// The flat entry on scalar parameters.  A struct passed by value is never preloaded; of scalar parameters the first 14 dwords arrive
+// in SGPRs with the wave (csrc/Makefile: -amdgpu-kernarg-preload-count for this translation unit), so what the data-moving waves need
+// in front of their first wait for arguments comes first: the descriptors' bases, the diagnostics pointer (tested by the kernel's first
+// instruction), the slice's K range and the per-lane source offsets (StreamOperand::init_flat; one output tile: Mtot and Ntot share a
+// dword).  The odometer's K group and the partials' address follow in StreamFlatTail, fetched by one round of scalar loads that the
+// per-lane setup covers.
+template <class Cfg>
+__global__ void __launch_bounds__(512, 2) gett_f32_stream_kernel(const float* A, const float* B, unsigned long long* timing, uint32_t nBlocks,
+                                                                 uint32_t kPerSlice, uint32_t kTotal, uint32_t sM, uint32_t sN, uint32_t mnTot,
+                                                                 uint32_t kStrideA0, uint32_t kStrideB0, const StreamFlatTail t) {
+    __shared__ __attribute__((aligned(16))) float lds[StreamFlatRing<Cfg>::FLOATS];
+    StreamFlatParams p;
+    p.A = A; p.B = B; p.partial = t.partial; p.timing = timing;
+    p.sM = sM; p.sN = sN; p.Mtot = mnTot & 0xffffu; p.Ntot = mnTot >> 16;
+    p.splitK = nBlocks; p.kPerSlice = kPerSlice; p.nBlocks = nBlocks; p.kTotal = kTotal;
+#pragma unroll
+    for (int i = 0; i < kMaxGroupModes; ++i) {
+        p.kExt[i] = t.kExt[i];
+        p.kStrideA[i] = (i == 0) ? kStrideA0 : t.kStrideA[i > 0 ? i - 1 : 0];
+        p.kStrideB[i] = (i == 0) ? kStrideB0 : t.kStrideB[i > 0 ? i - 1 : 0];
+        if (i < kMaxGroupModes - 1) p.kMagic[i] = t.kMagic[i];
+    }
+    p.kShifts = t.kShifts;
+    gett_f32_stream_flat_body<Cfg>(p, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -833,9 +899,8 @@ struct FoldFlatParams {
 // (0, 0: read from the block).  Nothing between the kernel's entry and its partial loads depends on more than the first
 // argument round; the decode of e and the output addresses sit between the loads' issue and the first use of their data.
 template <int NT, int FTM, int FTN>
-__global__ void __launch_bounds__(NT) splitk_reduce_frag_flat_kernel(const FoldFlatParams p) {
+__device__ __forceinline__ void splitk_fold_frag_flat_body(const FoldFlatParams& p, f32x4 (*red)[8]) {
     constexpr int G = NT / 8, U = 256 / G, W = NT / 64;
-    __shared__ f32x4 red[W][8];
     const int q = threadIdx.x & 7, g = threadIdx.x >> 3;
     const uint32_t e = blockIdx.x * 8 + q;
     const bool live = e < p.quadsTotal;
@@ -903,6 +968,30 @@ __global__ void __launch_bounds__(NT) splitk_reduce_frag_flat_kernel(const FoldF
     }
 }
 
+template <int NT, int FTM, int FTN>
+__global__ void __launch_bounds__(NT) splitk_reduce_frag_flat_kernel(const FoldFlatParams p) {
+    __shared__ f32x4 red[NT / 64][8];
+    splitk_fold_frag_flat_body<NT, FTM, FTN>(p, red);
+}
+
+// The same fold on scalar parameters: the first 14 dwords — all the partial loads and the output addresses need — arrive in SGPRs with
+// the wave (kernel-argument preload; a struct passed by value gets none), so no round of scalar loads stands in front of the
+// kernel's one memory round trip; the rest (C's side, beta, the run-time fragment counts) is fetched under the partial loads.
+template <int NT, int FTM, int FTN>
+__global__ void __launch_bounds__(NT) splitk_fold_frag_args_kernel(const float* partial, uint32_t splitK, uint32_t quadsTotal, float* D, int64_t sDm,
+                                                                   int64_t sDn, uint32_t tilesM, uint32_t Mtot, uint32_t Ntot, float alpha, float beta,
+                                                                   const float* C, int64_t sCm, int64_t sCn, uint32_t fragTM, uint32_t fragTN) {
+    __shared__ f32x4 red[NT / 64][8];
+    FoldFlatParams p;
+    p.partial = partial; p.splitK = splitK; p.quadsTotal = quadsTotal;
+    p.D = D; p.C = C;
+    p.sDm = sDm; p.sDn = sDn; p.sCm = sCm; p.sCn = sCn;
+    p.alpha = alpha; p.beta = beta;
+    p.tilesM = tilesM; p.Mtot = Mtot; p.Ntot = Ntot;
+    p.fragTM = fragTM; p.fragTN = fragTN;
+    splitk_fold_frag_flat_body<NT, FTM, FTN>(p, red);
+}
+
 hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t stream) {
     const size_t quads = (size_t)p.gL.total * p.tilesN * p.tilesM * 4u * p.fragTM * p.fragTN * 64u;
     const size_t blocks = (quads + 7) / 8;
@@ -921,7 +1010,17 @@ hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t st
         // 128 / 512 / 1024 threads per workgroup measured the same step time (43.6-44.0 us): the kernel is one memory
         // round trip plus launch, not throughput
         const dim3 grid((unsigned)blocks), block(256);
-        const uint32_t frag = (p.noFlatStart == 0 && p.fragTM == p.fragTN) ? p.fragTM : 0u;   // the GETT tiles are 64, 96 or 128 square
+        const uint32_t frag = (p.noFlatStart != FLAT_START_GENERAL && p.fragTM == p.fragTN) ? p.fragTM : 0u;   // the GETT tiles are 64, 96 or 128 square
+        if (p.noFlatStart == FLAT_START_ARGS || p.noFlatStart == FLAT_START_ARGS_FOLD) {    // the default: scalar parameters, preloaded
+#define CTAMD_FOLD_ARGS(FT) hipLaunchKernelGGL((splitk_fold_frag_args_kernel<256, FT, FT>), grid, block, 0, stream, f.partial, f.splitK, f.quadsTotal, f.D, \
+                                               f.sDm, f.sDn, f.tilesM, f.Mtot, f.Ntot, f.alpha, f.beta, f.C, f.sCm, f.sCn, f.fragTM, f.fragTN)
+            if (frag == 2u) CTAMD_FOLD_ARGS(2);
+            else if (frag == 3u) CTAMD_FOLD_ARGS(3);
+            else if (frag == 4u) CTAMD_FOLD_ARGS(4);
+            else CTAMD_FOLD_ARGS(0);
+#undef CTAMD_FOLD_ARGS
+            return hipGetLastError();
+        }
         if (frag == 2u) hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 2, 2>), grid, block, 0, stream, f);
         else if (frag == 3u) hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 3, 3>), grid, block, 0, stream, f);
         else if (frag == 4u) hipLaunchKernelGGL((splitk_reduce_frag_flat_kernel<256, 4, 4>), grid, block, 0, stream, f);
@@ -942,7 +1041,7 @@ std::atomic<uint64_t> g_flatStartLaunches{0};
 // K-tiles whose partials (default store policy) are folded by a second kernel.  Strides go in as bytes modulo 2^32 — what the general
 // entry computes from the same 64-bit strides (the planner ranks these kernels for operands whose byte span fits 32 bits).
 static bool flat_start_params(const GettParams& p, StreamFlatParams& f) {
-    if (p.noFlatStart != 0 || p.partial == nullptr || p.sync != nullptr || p.xcdTiles != 0 || p.partialPolicy != 0) return false;
+    if (p.noFlatStart == FLAT_START_GENERAL || p.partial == nullptr || p.sync != nullptr || p.xcdTiles != 0 || p.partialPolicy != 0) return false;
     if (p.gL.total != 1 || p.gM.n > 1 || p.gN.n > 1 || p.tilesM * p.tilesN != 1 || p.nBlocks != p.splitK) return false;
     if (p.gK.total % (uint32_t)kStreamBK != 0u || p.gK.div[0].d % (uint32_t)kStreamBK != 0u || (p.ragged & 1u) != 0u) return false;
     f.A = static_cast<const float*>(p.A);
@@ -981,9 +1080,25 @@ static hipError_t launch_stream(const GettParams& p, hipStream_t stream) {
     if constexpr (Cfg::BM == 96 && Cfg::BN == 96 && Cfg::S == 3 && (Cfg::ABL == 0 || Cfg::ABL == 5)) {
         StreamFlatParams f;
         if (flat_start_params(p, f)) {
-            using F = StreamCfg<96, 96, Cfg::LA, Cfg::LB, 3, Cfg::ABL == 0 ? 6 : 7>;
-            hipLaunchKernelGGL(gett_f32_stream_kernel<F>, dim3(p.nBlocks), dim3(512), 0, stream, f);
             g_flatStartLaunches.fetch_add(1, std::memory_order_relaxed);
+            if (p.noFlatStart == FLAT_START_ARGS || p.noFlatStart == FLAT_START_ARGS_GETT) {    // the default: scalar parameters, preloaded
+                using F = StreamCfg<96, 96, Cfg::LA, Cfg::LB, 3, Cfg::ABL == 0 ? 8 : 9>;
+                StreamFlatTail t;
+                t.partial = f.partial;
+                t.kShifts = f.kShifts;
+                for (int i = 0; i < kMaxGroupModes; ++i) {
+                    t.kExt[i] = f.kExt[i];
+                    if (i < kMaxGroupModes - 1) { t.kMagic[i] = f.kMagic[i]; t.kStrideA[i] = f.kStrideA[i + 1]; t.kStrideB[i] = f.kStrideB[i + 1]; }
+                }
+                void (*kernel)(const float*, const float*, unsigned long long*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                               const StreamFlatTail) = gett_f32_stream_kernel<F>;
+                hipLaunchKernelGGL(kernel, dim3(p.nBlocks), dim3(512), 0, stream, f.A, f.B, f.timing, f.nBlocks, f.kPerSlice, f.kTotal, f.sM, f.sN,
+                                   f.Mtot | (f.Ntot << 16), f.kStrideA[0], f.kStrideB[0], t);
+                return hipGetLastError();
+            }
+            using F = StreamCfg<96, 96, Cfg::LA, Cfg::LB, 3, Cfg::ABL == 0 ? 6 : 7>;
+            void (*kernel)(const StreamFlatParams) = gett_f32_stream_kernel<F>;
+            hipLaunchKernelGGL(kernel, dim3(p.nBlocks), dim3(512), 0, stream, f);
             return hipGetLastError();
         }
     }

@@ -99,6 +99,17 @@
 #define CTAMD_BODY_END(U) CTAMD_TILE_BODY(U, (U) == S - 1)
     if (r == S) {          // the common case (whole ring turns): straight-line code, no per-tile branch
         CTAMD_FOR_SLOTS(CTAMD_BODY_END)
+    } else if constexpr (Cfg::FLAT && CTAMD_FLAT_STRAIGHT_TAIL) {
+        // the flat entries (3-deep ring, 96 x 96: registers to spare): one or two tiles left, straight-line code on compile-time slots
+        // like the steady loop's — the rolled form below costs ~500 cycles more per tile (run-time slot addresses, fragment bases
+        // re-derived per use), and the headline's 32 K-tiles per slice always end in two of them
+        static_assert(S == 3, "the flat entries run the 3-deep ring");
+        if (r == 2) {
+            CTAMD_TILE_BODY(0, false)
+            CTAMD_TILE_BODY(1, true)
+        } else {
+            CTAMD_TILE_BODY(0, true)
+        }
     } else {
         // 1 .. S - 1 tiles left (slots 0 .. r - 1): ONE rolled copy of the tile body with run-time slot addresses.  (Unrolled
         // per slot with a branch on r in front of every copy, this tail alone spilled 90-180 VGPRs to scratch memory in the

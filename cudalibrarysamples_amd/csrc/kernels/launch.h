@@ -79,7 +79,7 @@ hipError_t launch_splitk_reduce(const SplitKReduceParams& p, hipStream_t stream)
 hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t stream);
 // streaming (LDS-DMA ring) kernels, gett_f32_stream.hip; gett_f32_kernels() returns the merged table
 const GettKernelInfo* gett_f32_stream_kernels(int* count);
-extern std::atomic<uint64_t> g_flatStartLaunches;   // launches of those kernels that took the flat entry (StreamFlatParams)
+extern std::atomic<uint64_t> g_flatStartLaunches;   // launches of those kernels that took a flat entry (StreamFlatParams, or scalar parameters)
 
 // bf16 / fp16 data, fp32 accumulation (v_mfma_f32_16x16x32_{bf16,f16}): the merged table, gett_h16.hip
 const GettKernelInfo* gett_h16_kernels(int* count);

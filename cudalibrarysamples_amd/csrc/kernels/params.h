@@ -74,9 +74,19 @@ struct GettParams {
     // tilesM2 x tilesN2 tiles from (mOrg2, nOrg2); tilesM2 * tilesN2 == 0: none.  The two edge strips of an output (rows past the
     // interior, columns past the interior) are ONE launch that way.
     uint32_t    tilesM2, tilesN2, mOrg2, nOrg2;
-    // test switch (CUTENSOR_AMD_FLAT_START=0, hooks flavour): the streaming fp32 kernels and their fold take the general entry also where
-    // the flat one applies (gett_f32_stream.hip, StreamFlatParams).  (Four bytes of the struct's tail padding: the block keeps its size.)
+    // test switch (CUTENSOR_AMD_FLAT_START, hooks flavour; a FlatStart value): which entry the streaming fp32 kernels and their fold take
+    // where the flat one applies (gett_f32_stream.hip).  (Four bytes of the struct's tail padding: the block keeps its size.)
     int32_t     noFlatStart;
+};
+
+// GettParams::noFlatStart / SplitKReduceParams::noFlatStart.  The switch's value: unset = FLAT_START_ARGS, '0' = FLAT_START_GENERAL,
+// '2' = FLAT_START_STRUCT, '3' / '4' = one of the two kernels on scalar parameters, the other on its struct (measurement)
+enum FlatStart : int32_t {
+    FLAT_START_ARGS = 0,        // flat entries on scalar, preloaded kernel parameters (the default)
+    FLAT_START_GENERAL = 1,     // the general entries
+    FLAT_START_STRUCT = 2,      // flat entries on StreamFlatParams / FoldFlatParams
+    FLAT_START_ARGS_FOLD = 3,   // fold on scalar parameters, GETT on StreamFlatParams
+    FLAT_START_ARGS_GETT = 4    // GETT on scalar parameters, fold on FoldFlatParams
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -103,6 +113,19 @@ struct StreamFlatParams {
     uint32_t     kStrideA[kMaxGroupModes], kStrideB[kMaxGroupModes];
 };
 static_assert(sizeof(StreamFlatParams) == 128, "the flat entry's arguments are two 64-byte lines");
+
+// What the flat entry on scalar parameters takes behind them (gett_f32_stream.hip): the rest of StreamFlatParams' K group (digit 0's
+// strides are scalar parameters) and the partials' address — nothing the first memory request's lane offsets need, and no word the
+// data-moving waves do not read (a dead word of a wide scalar load gives its register away, and the wave then waits for the load
+// before it may write that register).
+struct StreamFlatTail {
+    uint32_t     kExt[kMaxGroupModes];
+    uint32_t     kMagic[kMaxGroupModes - 1];
+    uint32_t     kShifts;
+    uint32_t     kStrideA[kMaxGroupModes - 1], kStrideB[kMaxGroupModes - 1];   // digits 1 ..
+    float*       partial;
+};
+static_assert(sizeof(StreamFlatTail) == 64, "one line, one round of scalar loads");
 
 // ---------------------------------------------------------------------------------------------
 // Contractions with more unfusable modes per group than kMaxGroupModes (e.g. the 25-mode extent-2 tensors of
