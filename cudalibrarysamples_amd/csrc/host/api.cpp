@@ -1829,6 +1829,9 @@ static cutensorStatus_t build_tiled(const PlanRequest& rq, cutensorPlan& pl, Til
     }
     if (!r.ch.empty()) pl.choice = r.ch[select_candidate(rq, pl, r.ch)];
     pl.planKind = pl.choice.kernel >= 0 ? PlanKind::Tiled : PlanKind::Simple;
+    // a one-tile split-K plan of the streaming fp32 kernel: the contracted digits in the order its operand stream prefers (the choice stands)
+    std::vector<CanonMode> kOrder;
+    if (r.mfmaPath && pl.planKind == PlanKind::Tiled && stream_k_order(pl.view, pl.choice, kOrder)) pl.view.K = std::move(kOrder);
     fill_gett_params(pl.view, pl.choice, pl.gett, pl.skr);
     set_conjugation(rq.desc, pl.view.swapped, pl.gett.conjA, pl.gett.conjB, pl.gett.conjC);
     pl.requiredWorkspace = pl.choice.workspace;

@@ -135,6 +135,9 @@ cutensorStatus_t build_contraction_view(const cutensorOperationDescriptor& op, C
 // Ranked candidate list (best first) under a workspace limit.
 std::vector<ContractionChoice> rank_contraction_choices(const ContractionView& v, uint64_t wsLimit,
                                                         int numCUs, bool operandsStreamed = false);
+// The order of the contracted digits a one-tile split-K plan of the streaming fp32 kernel runs on when exactly one operand is
+// K-contiguous: that operand's stride-1 digit first, the others by the OTHER operand's strides.  True: `K` holds it and differs from v.K.
+bool stream_k_order(const ContractionView& v, const ContractionChoice& c, std::vector<CanonMode>& K);
 bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, ContractionChoice& c);
 // general MFMA family (kernels/gett_gen.inc): false only for fp32 data and for views the tiled kernels cannot describe
 // (f32xElem: fp32 data under a reduced-precision compute descriptor — GEN_F32_BF16 / GEN_F32_F16 / GEN_F32_BF16X3, gett_gen_f32x.inc)

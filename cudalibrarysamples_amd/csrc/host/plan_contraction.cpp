@@ -13,7 +13,9 @@
 //      neighbours that are jointly contiguous in every tensor that carries them ("mode fusion");
 //   5. decide, per operand, whether 16-byte lanes can run along a free mode (LAY_F), along the
 //      contracted mode (LAY_K), or not at all (LAY_S);
-//   6. rank (tile shape, split-K) candidates with a small roofline cost model.
+//   6. rank (tile shape, split-K) candidates with a small roofline cost model;
+//   7. for a one-tile split-K plan of the streaming fp32 kernel, put the contracted digits above the first one in the order of the
+//      operand that is NOT K-contiguous (stream_k_order: after the kernel is chosen, the choice stands).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -317,6 +319,44 @@ cutensorStatus_t build_contraction_view(const cutensorOperationDescriptor& op, C
 // (a partial unit may reach past the end of the tensor: the RAG descriptors end with it)
 static bool f32_needs_rag(const ContractionView& v) {
     return v.totK % 32 != 0 || !v.lanesA || !v.lanesB;
+}
+
+// The contracted digits of a one-tile split-K plan of the streaming kernel, ordered for the operand stream.  build_contraction_view
+// sorts K by the strides of the K-contiguous operand; when only ONE operand is K-contiguous, the other one then reads rows that lie
+// far apart in consecutive K-tiles (the headline 'abcd,dcbe->ae': B's rows of 384 bytes 24 KB or 1.5 MB apart).  Here the stride-1
+// digit stays first — the K-contiguous operand keeps its 128-byte rows in LDS — and the remaining digits follow the OTHER operand's
+// strides, smallest first: a workgroup's consecutive K-tiles read neighbouring rows of it.  No digit is split.  Measured on the
+// headline: the operand stream alone 33.6 -> 30.2 us, the step 40.0 -> 39.3 us — the slowest workgroup, not the mean one, gets
+// faster (profiles/korder_*).
+// Adopted after the kernel is chosen, and only where the launch is one the flat entry covers (gett_f32_stream.hip, launch_stream /
+// flat_start_params): the 96 x 96 tile on the 3-deep ring, one output tile, one M and one N mode, no batch, slices of whole K-tiles (the last
+// one may be shorter), a first digit that holds whole K-tiles, at most kMaxGroupModes digits.  The ranking reads nothing of the view that the
+// order changes (K's total, the first digit and the spans stay), so kernel, split and slice length stand.  Every other plan keeps the
+// view's order, and so does every plan under CUTENSOR_AMD_KORDER (hooks flavour: "A" is the view's own order).
+bool stream_k_order(const ContractionView& v, const ContractionChoice& c, std::vector<CanonMode>& K) {
+    if (v.dtype != HIP_R_32F || v.wide || c.family != 0 || c.kernel < 0 || c.splitK <= 1 || v.K.size() < 3) return false;
+    if (const char* korder = CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER"))
+        if (korder[0]) return false;
+    int count = 0;
+    const GettKernelInfo* tab = gett_f32_kernels(&count);
+    if (c.kernel >= count) return false;
+    const GettKernelInfo& k = tab[c.kernel];
+    if (!k.fragPartials || k.ablation || k.bm != 96 || k.bn != 96 || k.pf != 3) return false;             // the kernels that have a flat twin
+    if (v.totL != 1 || v.M.size() > 1 || v.N.size() > 1 || v.totM > (uint64_t)k.bm || v.totN > (uint64_t)k.bn) return false;
+    if (f32_needs_rag(v) || v.totK % (uint64_t)k.bk != 0 || c.kPerSlice % (uint32_t)k.bk != 0) return false;
+    bool kContigA = false, kContigB = false;
+    for (const CanonMode& m : v.K) { kContigA |= (m.sA == 1); kContigB |= (m.sB == 1); }
+    if (kContigA == kContigB) return false;                                                               // exactly one K-contiguous operand
+    const bool otherIsB = kContigA;
+    if ((otherIsB ? v.K.front().sA : v.K.front().sB) != 1) return false;                                  // (its stride-1 digit leads the view)
+    K = v.K;
+    std::stable_sort(K.begin() + 1, K.end(), [otherIsB](const CanonMode& x, const CanonMode& y) { return otherIsB ? x.sB < y.sB : x.sA < y.sA; });
+    fuse_group(K, true, true, false);
+    if (K.front().extent % k.bk != 0 || (int)K.size() > kMaxGroupModes) return false;
+    if (K.size() != v.K.size()) return true;
+    for (size_t i = 0; i < K.size(); ++i)
+        if (K[i].label != v.K[i].label || K[i].extent != v.K[i].extent) return true;
+    return false;                                                                                         // the order the view has
 }
 
 // ---------------------------------------------------------------------------------------------
