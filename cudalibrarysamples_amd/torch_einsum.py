@@ -136,15 +136,29 @@ def _alloc_workspace(nbytes, device):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def _get_workspace(device, nbytes):
-    """One growing workspace buffer per device, exactly as large as the largest plan so far asked for (the plan reports
-    CUTENSOR_PLAN_REQUIRED_WORKSPACE; python/einsum.h:365-392)."""
+def _get_workspace(device, nbytes, stream=None):
+    """One growing workspace buffer per (device, stream), exactly as large as the largest plan so far asked for on that stream (the plan
+    reports CUTENSOR_PLAN_REQUIRED_WORKSPACE; python/einsum.h:365-392).  stream: a torch.cuda.Stream, or the raw handle of the current
+    stream; None: the device's current stream, the one EinsumPlan.execute launches on.
+
+    Two streams never share a buffer: einsums that run side by side on two streams would otherwise write their split-K partials into the
+    same memory.  A buffer is allocated with its stream current, so the caching allocator ties the block to that stream: when the buffer
+    grows and the old one is dropped, the block can only be handed out again to work that is ordered after its last use (the reference
+    binding gets the same from at::empty per call, einsum.cc:75-137).  A stream's buffer lives until _workspace.clear()."""
     if not nbytes:
         return None
-    ws = _workspace.get(device)
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    key = (device, getattr(stream, "cuda_stream", stream))
+    ws = _workspace.get(key)
     if ws is None or ws.numel() < nbytes:
-        _workspace.pop(device, None)
-        ws = _workspace[device] = _alloc_workspace(nbytes, device)
+        _workspace.pop(key, None)
+        if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(device):
+            with torch.cuda.stream(stream):
+                ws = _alloc_workspace(nbytes, device)
+        else:
+            ws = _alloc_workspace(nbytes, device)
+        _workspace[key] = ws
     return ws
 
 
