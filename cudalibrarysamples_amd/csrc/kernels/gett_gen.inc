@@ -30,23 +30,9 @@
 // Split-K (few output tiles, long K): every slice writes its tile in the accumulator type, a second small kernel folds.
 //
 // Included by gett_gen_h16.hip / gett_gen_f64.hip / gett_gen_cplx.hip, which instantiate their part of the table.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "params.h"
-#include "launch.h"
-#include "gett_common.h"
-#include "gett_gen_layout.h"
+#include "gett_gen_common.h"
 
 namespace ctamd {
-
-typedef double   f64x4 __attribute__((ext_vector_type(4)));
-typedef double   f64x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef short    g16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16   gbf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 gf16x8 __attribute__((ext_vector_type(8)));
 
 template <int GE> struct GenElemTraits;
 template <> struct GenElemTraits<GEN_BF16> { static constexpr int ES = 2;  static constexpr bool ACC64 = false, CPLX = false; };
@@ -245,10 +231,7 @@ __global__ void __launch_bounds__(256, 2) gett_gen_kernel(const GettParams p) {
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        if constexpr (GE == GEN_BF16)
-                            acc[i][j].v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gbf16x8, fa[i]), __builtin_bit_cast(gbf16x8, fb[j]), acc[i][j].v, 0, 0, 0);
-                        else
-                            acc[i][j].v = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gf16x8, fa[i]), __builtin_bit_cast(gf16x8, fb[j]), acc[i][j].v, 0, 0, 0);
+                        acc[i][j].v = gen_mfma16<GE == GEN_F16>(fa[i], fb[j], acc[i][j].v);
                     }
             } else if constexpr (GE == GEN_F64) {
                 f64x4 fa[TM], fb[TN];       // elements k = 4 q + j of the row
@@ -373,7 +356,6 @@ __global__ void __launch_bounds__(256, 2) gett_gen_kernel(const GettParams p) {
                     if constexpr (ES == 2) p.partial[e] = acc[i][j].v[t];
                     else if constexpr (GE == GEN_F64) reinterpret_cast<double*>(p.partial)[e] = acc[i][j].v[t];
                     else if constexpr (GE == GEN_C32) {
-                        typedef float f32x2 __attribute__((ext_vector_type(2)));
                         reinterpret_cast<f32x2*>(p.partial)[e] = f32x2{acc[i][j].rr[t] - acc[i][j].ii[t], acc[i][j].x[t]};
                     } else
                         reinterpret_cast<f64x2*>(p.partial)[e] = f64x2{acc[i][j].rr[t] - acc[i][j].ii[t], acc[i][j].x[t]};
@@ -436,7 +418,6 @@ __global__ void __launch_bounds__(256, 2) gett_gen_kernel(const GettParams p) {
                         oRe += beRe * cRe - beIm * cIm;
                         oIm += beRe * cIm + beIm * cRe;
                     }
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<f32x2*>(static_cast<float*>(p.D) + 2 * oD) = f32x2{oRe, oIm};
                 } else {
                     const double re = acc[i][j].rr[t] - acc[i][j].ii[t], im = acc[i][j].x[t];
@@ -454,21 +435,6 @@ __global__ void __launch_bounds__(256, 2) gett_gen_kernel(const GettParams p) {
         }
 }
 
-template <class Cfg>
-static hipError_t launch_gen(const GettParams& p, hipStream_t stream) {
-    if (p.nBlocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(gett_gen_kernel<Cfg>, dim3(p.nBlocks), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-// table entry: {bm, bn, bk, wm, wn, wk, layA, layB, threads, pf, kfast, ablation, launch, fragPartials, nt, elem, vec}
-#define CTAMD_GEN_ENTRY(GE, BM, BN, BK, OA, OB, V) \
-    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen<GenCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V, "gett_gen_kernel"},
-// the four orientation pairs (LAY_F = 0: free-contiguous, LAY_K = 1: K-contiguous) of one (type, tile, vector width)
-#define CTAMD_GEN_ORIENTS(GE, BM, BN, BK, V)   \
-    CTAMD_GEN_ENTRY(GE, BM, BN, BK, 0, 0, V)   \
-    CTAMD_GEN_ENTRY(GE, BM, BN, BK, 0, 1, V)   \
-    CTAMD_GEN_ENTRY(GE, BM, BN, BK, 1, 0, V)   \
-    CTAMD_GEN_ENTRY(GE, BM, BN, BK, 1, 1, V)
+#define CTAMD_GEN_ORIENTS(GE, BM, BN, BK, V) CTAMD_GEN_FAMILY_ORIENTS(gett_gen_kernel, GenCfg, GE, BM, BN, BK, V)
 
 }  // namespace ctamd

@@ -23,55 +23,22 @@
 // infinite sum stays infinite), C never read when beta == 0; float2
 // partials [slice][L][M][N] folded by the complex64 branch of launch_gen_splitk_reduce.
 //
-// Non-finite values under TF32: a part whose bf16 rounding is not finite goes to the LO plane whole, with hi = 0 (F32xCvt-style), so that
+// Non-finite values under TF32: a part whose bf16 rounding is not finite goes to the LO plane whole, with hi = 0 (Gen16Cvt), so that
 // inf * y arrives as lo_x * hi_y with the right sign and the other two terms are 0 * finite.  Two non-finite factors in one product: NaN.
 //
 // LDS (static, two stages) and registers:  128 x 128 x 32 — 16BF / 16F: 64 KiB, TF32: 128 KiB; 128 accumulator registers, one workgroup
 // per CU (__launch_bounds__(256, 1)).  64 x 64 x 32 — 32 / 64 KiB, two workgroups per CU (__launch_bounds__(256, 2)).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "params.h"
-#include "launch.h"
-#include "gett_common.h"
-#include "gett_gen_layout.h"
+#include "gett_gen_common.h"
 
 namespace ctamd {
-
-typedef float    cx_f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t cx_u32x4 __attribute__((ext_vector_type(4)));
-typedef short    cx_g16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16   cx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cx_f16x8 __attribute__((ext_vector_type(8)));
-
-// one fp32 part -> the 16-bit pattern(s) of the mode.  PLANES = 2: (hi, lo) of the three-term split.
-template <int GE> struct C32xCvt;
-template <> struct C32xCvt<GEN_C32_BF16> {
-    static constexpr int PLANES = 1;
-    static __device__ __forceinline__ void cvt(float x, uint16_t (&o)[1]) { o[0] = __builtin_bit_cast(uint16_t, (__bf16)x); }
-};
-template <> struct C32xCvt<GEN_C32_F16> {
-    static constexpr int PLANES = 1;
-    static __device__ __forceinline__ void cvt(float x, uint16_t (&o)[1]) { o[0] = __builtin_bit_cast(uint16_t, (_Float16)x); }
-};
-template <> struct C32xCvt<GEN_C32_BF16X3> {
-    static constexpr int PLANES = 2;
-    static __device__ __forceinline__ void cvt(float x, uint16_t (&o)[2]) {
-        const __bf16 hi = (__bf16)x;
-        const uint16_t hb = __builtin_bit_cast(uint16_t, hi);
-        const bool finite = (hb & 0x7f80u) != 0x7f80u;
-        const float rest = finite ? x - (float)hi : x;      // exact; a non-finite value goes to the lo plane whole
-        o[0] = finite ? hb : (uint16_t)0;
-        o[1] = __builtin_bit_cast(uint16_t, (__bf16)rest);
-    }
-};
 
 template <int GE_, int BM_, int BN_, int BK_, int OA_, int OB_, int V_>
 struct C32xCfg {
     static constexpr int GE = GE_, BM = BM_, BN = BN_, BK = BK_, OA = OA_, OB = OB_, V = V_;
     static constexpr int WM = 2, WN = 2, THREADS = 256;
     static constexpr int TM = BM / (WM * 16), TN = BN / (WN * 16);
-    static constexpr int PLANES = C32xCvt<GE>::PLANES;
+    using Cvt = Gen16Cvt<GE - GEN_C32_BF16>;      // one fp32 part -> the 16-bit pattern(s) of the mode
+    static constexpr int PLANES = Cvt::PLANES;
     static constexpr int IMAGES = 2 * PLANES;                         // per operand: (re, im) x planes
     static constexpr int WGS = (BM * BN <= 64 * 64) ? 2 : 1;          // workgroups per CU the registers and the LDS are budgeted for
     static constexpr int LDS_BYTES = 2 * IMAGES * (BM + BN) * BK * 2;  // two stages
@@ -83,11 +50,10 @@ struct C32xCfg {
 // ---------------------------------------------------------------------------------------------
 // One operand of the K-tile: global complex64 -> registers -> the (rounded) 16-bit images of its real and imaginary parts.
 // ---------------------------------------------------------------------------------------------
-template <int GE, int ORIENT, int ROWS, int BK, int V>
+template <class Cvt, int ORIENT, int ROWS, int BK, int V>
 struct C32xOperand {
     using Map = GenUnitMap<ORIENT, ROWS, BK, V, 256>;
     using Img = GenImage<2, BK>;
-    using Cvt = C32xCvt<GE>;
     static constexpr int NU = Map::NU;
     static constexpr int PLANES = Cvt::PLANES;
     static constexpr int PLANE_BYTES = ROWS * Img::RB;
@@ -124,7 +90,7 @@ struct C32xOperand {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(src);
                 st[i][0] = v[0]; st[i][1] = v[1]; st[i][2] = v[2]; st[i][3] = v[3];
             } else {
-                const cx_f32x2 v = *reinterpret_cast<const cx_f32x2*>(src);
+                const f32x2 v = *reinterpret_cast<const f32x2*>(src);
                 st[i][0] = v[0]; st[i][1] = v[1];
             }
         }
@@ -170,8 +136,8 @@ template <class Cfg>
 __global__ void __launch_bounds__(256, Cfg::WGS) gett_gen_c32x_kernel(const GettParams p) {
     constexpr int GE = Cfg::GE, BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, V = Cfg::V;
     constexpr int WM = Cfg::WM, TM = Cfg::TM, TN = Cfg::TN, PLANES = Cfg::PLANES;
-    using OpA = C32xOperand<GE, Cfg::OA, BM, BK, V>;
-    using OpB = C32xOperand<GE, Cfg::OB, BN, BK, V>;
+    using OpA = C32xOperand<typename Cfg::Cvt, Cfg::OA, BM, BK, V>;
+    using OpB = C32xOperand<typename Cfg::Cvt, Cfg::OB, BN, BK, V>;
     using Img = GenImage<2, BK>;
     using Frag = GenFrag<2>;
     constexpr int STAGE = OpA::LDS_BYTES + OpB::LDS_BYTES;
@@ -220,16 +186,11 @@ __global__ void __launch_bounds__(256, Cfg::WGS) gett_gen_c32x_kernel(const Gett
 #pragma unroll
     for (int s = 0; s < KB; ++s) fragOff[s] = Img::unit_addr(0, r, Frag::unit(s, q, 0));
 
-    auto mfma = [](const cx_g16x8& a, const cx_g16x8& b, f32x4 c) {
-        if constexpr (GE == GEN_C32_F16)
-            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cx_f16x8, a), __builtin_bit_cast(cx_f16x8, b), c, 0, 0, 0);
-        else
-            return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cx_bf16x8, a), __builtin_bit_cast(cx_bf16x8, b), c, 0, 0, 0);
-    };
+    constexpr bool F16 = GE == GEN_C32_F16;
     // -x in every 16-bit element: the sign bits of both halves of each register
-    auto negated = [](const cx_g16x8& a) {
-        const cx_u32x4 w = __builtin_bit_cast(cx_u32x4, a) ^ cx_u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
-        return __builtin_bit_cast(cx_g16x8, w);
+    auto negated = [](const g16x8& a) {
+        const u32x4 w = __builtin_bit_cast(u32x4, a) ^ u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
+        return __builtin_bit_cast(g16x8, w);
     };
 
     auto compute = [&](const char* buf) {
@@ -237,39 +198,39 @@ __global__ void __launch_bounds__(256, Cfg::WGS) gett_gen_c32x_kernel(const Gett
         const char* lb = buf + OpA::LDS_BYTES + (wn * (BN / Cfg::WN)) * Img::RB;
 #pragma unroll
         for (int s = 0; s < KB; ++s) {
-            cx_g16x8 fb[2][PLANES][TN];      // [part][plane][fragment]
+            g16x8 fb[2][PLANES][TN];      // [part][plane][fragment]
 #pragma unroll
             for (int part = 0; part < 2; ++part)
 #pragma unroll
                 for (int pl = 0; pl < PLANES; ++pl)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        fb[part][pl][j] = *reinterpret_cast<const cx_g16x8*>(lb + OpB::image(part, pl) + 16 * j * Img::RB + fragOff[s]);
+                        fb[part][pl][j] = *reinterpret_cast<const g16x8*>(lb + OpB::image(part, pl) + 16 * j * Img::RB + fragOff[s]);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                cx_g16x8 ar[PLANES], ai[PLANES], an[PLANES];      // a_r, a_i, -a_i
+                g16x8 ar[PLANES], ai[PLANES], an[PLANES];      // a_r, a_i, -a_i
 #pragma unroll
                 for (int pl = 0; pl < PLANES; ++pl) {
-                    ar[pl] = *reinterpret_cast<const cx_g16x8*>(la + OpA::image(0, pl) + 16 * i * Img::RB + fragOff[s]);
-                    ai[pl] = *reinterpret_cast<const cx_g16x8*>(la + OpA::image(1, pl) + 16 * i * Img::RB + fragOff[s]);
+                    ar[pl] = *reinterpret_cast<const g16x8*>(la + OpA::image(0, pl) + 16 * i * Img::RB + fragOff[s]);
+                    ai[pl] = *reinterpret_cast<const g16x8*>(la + OpA::image(1, pl) + 16 * i * Img::RB + fragOff[s]);
                     an[pl] = negated(ai[pl]);
                 }
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     if constexpr (PLANES == 2) {      // the small terms first, then hi * hi: all into the same two accumulators
-                        accRe[i][j] = mfma(an[1], fb[1][0][j], accRe[i][j]);
-                        accRe[i][j] = mfma(an[0], fb[1][1][j], accRe[i][j]);
-                        accRe[i][j] = mfma(ar[1], fb[0][0][j], accRe[i][j]);
-                        accRe[i][j] = mfma(ar[0], fb[0][1][j], accRe[i][j]);
-                        accIm[i][j] = mfma(ai[1], fb[0][0][j], accIm[i][j]);
-                        accIm[i][j] = mfma(ai[0], fb[0][1][j], accIm[i][j]);
-                        accIm[i][j] = mfma(ar[1], fb[1][0][j], accIm[i][j]);
-                        accIm[i][j] = mfma(ar[0], fb[1][1][j], accIm[i][j]);
+                        accRe[i][j] = gen_mfma16<F16>(an[1], fb[1][0][j], accRe[i][j]);
+                        accRe[i][j] = gen_mfma16<F16>(an[0], fb[1][1][j], accRe[i][j]);
+                        accRe[i][j] = gen_mfma16<F16>(ar[1], fb[0][0][j], accRe[i][j]);
+                        accRe[i][j] = gen_mfma16<F16>(ar[0], fb[0][1][j], accRe[i][j]);
+                        accIm[i][j] = gen_mfma16<F16>(ai[1], fb[0][0][j], accIm[i][j]);
+                        accIm[i][j] = gen_mfma16<F16>(ai[0], fb[0][1][j], accIm[i][j]);
+                        accIm[i][j] = gen_mfma16<F16>(ar[1], fb[1][0][j], accIm[i][j]);
+                        accIm[i][j] = gen_mfma16<F16>(ar[0], fb[1][1][j], accIm[i][j]);
                     }
-                    accRe[i][j] = mfma(an[0], fb[1][0][j], accRe[i][j]);
-                    accRe[i][j] = mfma(ar[0], fb[0][0][j], accRe[i][j]);
-                    accIm[i][j] = mfma(ai[0], fb[0][0][j], accIm[i][j]);
-                    accIm[i][j] = mfma(ar[0], fb[1][0][j], accIm[i][j]);
+                    accRe[i][j] = gen_mfma16<F16>(an[0], fb[1][0][j], accRe[i][j]);
+                    accRe[i][j] = gen_mfma16<F16>(ar[0], fb[0][0][j], accRe[i][j]);
+                    accIm[i][j] = gen_mfma16<F16>(ai[0], fb[0][0][j], accIm[i][j]);
+                    accIm[i][j] = gen_mfma16<F16>(ar[0], fb[1][0][j], accIm[i][j]);
                 }
             }
         }
@@ -318,7 +279,7 @@ __global__ void __launch_bounds__(256, Cfg::WGS) gett_gen_c32x_kernel(const Gett
                 for (int j = 0; j < TN; ++j) {
                     const uint32_t n = nBase + 16 * j + r;
                     if (n >= Ntot) continue;
-                    reinterpret_cast<cx_f32x2*>(p.partial)[tileOff + (size_t)m * Ntot + n] = cx_f32x2{accRe[i][j][t], accIm[i][j][t]};
+                    reinterpret_cast<f32x2*>(p.partial)[tileOff + (size_t)m * Ntot + n] = f32x2{accRe[i][j][t], accIm[i][j][t]};
                 }
             }
         return;
@@ -364,26 +325,11 @@ __global__ void __launch_bounds__(256, Cfg::WGS) gett_gen_c32x_kernel(const Gett
                     oRe += beRe * cRe - beIm * cIm;
                     oIm += beRe * cIm + beIm * cRe;
                 }
-                *reinterpret_cast<cx_f32x2*>(static_cast<float*>(p.D) + 2 * oD) = cx_f32x2{oRe, oIm};
+                *reinterpret_cast<f32x2*>(static_cast<float*>(p.D) + 2 * oD) = f32x2{oRe, oIm};
             }
         }
 }
 
-template <class Cfg>
-static hipError_t launch_gen_c32x(const GettParams& p, hipStream_t stream) {
-    if (p.nBlocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(gett_gen_c32x_kernel<Cfg>, dim3(p.nBlocks), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-// table entry: {bm, bn, bk, wm, wn, wk, layA, layB, threads, pf, kfast, ablation, launch, fragPartials, nt, elem, vec}
-#define CTAMD_C32X_ENTRY(GE, BM, BN, BK, OA, OB, V) \
-    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen_c32x<C32xCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V, "gett_gen_c32x_kernel"},
-// the four orientation pairs (LAY_F = 0: free-contiguous, LAY_K = 1: K-contiguous) of one (mode, tile, vector width)
-#define CTAMD_C32X_ORIENTS(GE, BM, BN, BK, V)   \
-    CTAMD_C32X_ENTRY(GE, BM, BN, BK, 0, 0, V)   \
-    CTAMD_C32X_ENTRY(GE, BM, BN, BK, 0, 1, V)   \
-    CTAMD_C32X_ENTRY(GE, BM, BN, BK, 1, 0, V)   \
-    CTAMD_C32X_ENTRY(GE, BM, BN, BK, 1, 1, V)
+#define CTAMD_C32X_ORIENTS(GE, BM, BN, BK, V) CTAMD_GEN_FAMILY_ORIENTS(gett_gen_c32x_kernel, C32xCfg, GE, BM, BN, BK, V)
 
 }  // namespace ctamd

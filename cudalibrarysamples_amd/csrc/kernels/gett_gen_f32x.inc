@@ -22,50 +22,17 @@
 // a bf16 value.)  Two non-finite factors meeting in one product give NaN.
 //
 // LDS budget (static, two stages): 128 x 128 x 64 one image: 64 KiB; 128 x 128 x 32 two images: 64 KiB; two workgroups per CU.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "params.h"
-#include "launch.h"
-#include "gett_common.h"
-#include "gett_gen_layout.h"
+#include "gett_gen_common.h"
 
 namespace ctamd {
-
-typedef uint32_t x_u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t x_u32x4 __attribute__((ext_vector_type(4)));
-typedef short    x_g16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16   x_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 x_f16x8 __attribute__((ext_vector_type(8)));
-
-// fp32 -> the 16-bit pattern(s) of the mode.  PLANES = 2: (hi, lo) of the three-term split.
-template <int GE> struct F32xCvt;
-template <> struct F32xCvt<GEN_F32_BF16> {
-    static constexpr int PLANES = 1;
-    static __device__ __forceinline__ void cvt(float x, uint16_t (&o)[1]) { o[0] = __builtin_bit_cast(uint16_t, (__bf16)x); }
-};
-template <> struct F32xCvt<GEN_F32_F16> {
-    static constexpr int PLANES = 1;
-    static __device__ __forceinline__ void cvt(float x, uint16_t (&o)[1]) { o[0] = __builtin_bit_cast(uint16_t, (_Float16)x); }
-};
-template <> struct F32xCvt<GEN_F32_BF16X3> {
-    static constexpr int PLANES = 2;
-    static __device__ __forceinline__ void cvt(float x, uint16_t (&o)[2]) {
-        const __bf16 hi = (__bf16)x;
-        const uint16_t hb = __builtin_bit_cast(uint16_t, hi);
-        const bool finite = (hb & 0x7f80u) != 0x7f80u;
-        const float rest = finite ? x - (float)hi : x;      // exact; a non-finite value goes to the lo plane whole
-        o[0] = finite ? hb : (uint16_t)0;
-        o[1] = __builtin_bit_cast(uint16_t, (__bf16)rest);
-    }
-};
 
 template <int GE_, int BM_, int BN_, int BK_, int OA_, int OB_, int V_>
 struct F32xCfg {
     static constexpr int GE = GE_, BM = BM_, BN = BN_, BK = BK_, OA = OA_, OB = OB_, V = V_;
     static constexpr int WM = 2, WN = 2, THREADS = 256;
     static constexpr int TM = BM / (WM * 16), TN = BN / (WN * 16);
-    static constexpr int PLANES = F32xCvt<GE>::PLANES;
+    using Cvt = Gen16Cvt<GE - GEN_F32_BF16>;
+    static constexpr int PLANES = Cvt::PLANES;
     static_assert(BM % 32 == 0 && BN % 32 == 0, "wave sub-tiles are 16-granular");
     static_assert(V == 4 || V == 1, "16-byte loads or 4-byte gathers");
 };
@@ -73,11 +40,10 @@ struct F32xCfg {
 // ---------------------------------------------------------------------------------------------
 // One operand of the K-tile: global fp32 -> registers -> (rounded) 16-bit LDS image(s).
 // ---------------------------------------------------------------------------------------------
-template <int GE, int ORIENT, int ROWS, int BK, int V>
+template <class Cvt, int ORIENT, int ROWS, int BK, int V>
 struct F32xOperand {
     using Map = GenUnitMap<ORIENT, ROWS, BK, V, 256>;
     using Img = GenImage<2, BK>;
-    using Cvt = F32xCvt<GE>;
     static constexpr int NU = Map::NU;
     static constexpr int PLANE_BYTES = ROWS * Img::RB;
     static constexpr int LDS_BYTES = Cvt::PLANES * PLANE_BYTES;
@@ -133,8 +99,8 @@ struct F32xOperand {
                     *reinterpret_cast<uint16_t*>(base + Img::addr(row, kl)) = h[0][pl];
                 } else if constexpr (ORIENT == 1) {
                     // four consecutive k of one row: 8 bytes inside one 16-byte unit of the image
-                    *reinterpret_cast<x_u32x2*>(base + Img::addr(row, kl)) =
-                        x_u32x2{(uint32_t)h[0][pl] | ((uint32_t)h[1][pl] << 16), (uint32_t)h[2][pl] | ((uint32_t)h[3][pl] << 16)};
+                    *reinterpret_cast<u32x2*>(base + Img::addr(row, kl)) =
+                        u32x2{(uint32_t)h[0][pl] | ((uint32_t)h[1][pl] << 16), (uint32_t)h[2][pl] | ((uint32_t)h[3][pl] << 16)};
                 } else {
                     // free-contiguous unit: V rows at one k — the transposition happens here
 #pragma unroll
@@ -149,8 +115,8 @@ template <class Cfg>
 __global__ void __launch_bounds__(256, 2) gett_gen_f32x_kernel(const GettParams p) {
     constexpr int GE = Cfg::GE, BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, V = Cfg::V;
     constexpr int WM = Cfg::WM, TM = Cfg::TM, TN = Cfg::TN, PLANES = Cfg::PLANES;
-    using OpA = F32xOperand<GE, Cfg::OA, BM, BK, V>;
-    using OpB = F32xOperand<GE, Cfg::OB, BN, BK, V>;
+    using OpA = F32xOperand<typename Cfg::Cvt, Cfg::OA, BM, BK, V>;
+    using OpB = F32xOperand<typename Cfg::Cvt, Cfg::OB, BN, BK, V>;
     using Img = GenImage<2, BK>;
     using Frag = GenFrag<2>;
     constexpr int STAGE = OpA::LDS_BYTES + OpB::LDS_BYTES;
@@ -195,35 +161,29 @@ __global__ void __launch_bounds__(256, 2) gett_gen_f32x_kernel(const GettParams 
 #pragma unroll
     for (int s = 0; s < KB; ++s) fragOff[s] = Img::unit_addr(0, r, Frag::unit(s, q, 0));
 
-    auto mfma = [](const x_g16x8& a, const x_g16x8& b, f32x4 c) {
-        if constexpr (GE == GEN_F32_F16)
-            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(x_f16x8, a), __builtin_bit_cast(x_f16x8, b), c, 0, 0, 0);
-        else
-            return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(x_bf16x8, a), __builtin_bit_cast(x_bf16x8, b), c, 0, 0, 0);
-    };
-
+    constexpr bool F16 = GE == GEN_F32_F16;
     auto compute = [&](const char* buf) {
         const char* la = buf + (wm * (BM / WM)) * Img::RB;
         const char* lb = buf + OpA::LDS_BYTES + (wn * (BN / Cfg::WN)) * Img::RB;
 #pragma unroll
         for (int s = 0; s < KB; ++s) {
-            x_g16x8 fa[PLANES][TM], fb[PLANES][TN];
+            g16x8 fa[PLANES][TM], fb[PLANES][TN];
 #pragma unroll
             for (int pl = 0; pl < PLANES; ++pl) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) fa[pl][i] = *reinterpret_cast<const x_g16x8*>(la + pl * OpA::PLANE_BYTES + 16 * i * Img::RB + fragOff[s]);
+                for (int i = 0; i < TM; ++i) fa[pl][i] = *reinterpret_cast<const g16x8*>(la + pl * OpA::PLANE_BYTES + 16 * i * Img::RB + fragOff[s]);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) fb[pl][j] = *reinterpret_cast<const x_g16x8*>(lb + pl * OpB::PLANE_BYTES + 16 * j * Img::RB + fragOff[s]);
+                for (int j = 0; j < TN; ++j) fb[pl][j] = *reinterpret_cast<const g16x8*>(lb + pl * OpB::PLANE_BYTES + 16 * j * Img::RB + fragOff[s]);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     if constexpr (PLANES == 2) {      // the two small terms first, then hi * hi: all into the same accumulator
-                        acc[i][j] = mfma(fa[1][i], fb[0][j], acc[i][j]);
-                        acc[i][j] = mfma(fa[0][i], fb[1][j], acc[i][j]);
+                        acc[i][j] = gen_mfma16<F16>(fa[1][i], fb[0][j], acc[i][j]);
+                        acc[i][j] = gen_mfma16<F16>(fa[0][i], fb[1][j], acc[i][j]);
                     }
-                    acc[i][j] = mfma(fa[0][i], fb[0][j], acc[i][j]);
+                    acc[i][j] = gen_mfma16<F16>(fa[0][i], fb[0][j], acc[i][j]);
                 }
         }
     };
@@ -312,21 +272,6 @@ __global__ void __launch_bounds__(256, 2) gett_gen_f32x_kernel(const GettParams 
         }
 }
 
-template <class Cfg>
-static hipError_t launch_gen_f32x(const GettParams& p, hipStream_t stream) {
-    if (p.nBlocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(gett_gen_f32x_kernel<Cfg>, dim3(p.nBlocks), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-// table entry: {bm, bn, bk, wm, wn, wk, layA, layB, threads, pf, kfast, ablation, launch, fragPartials, nt, elem, vec}
-#define CTAMD_F32X_ENTRY(GE, BM, BN, BK, OA, OB, V) \
-    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen_f32x<F32xCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V, "gett_gen_f32x_kernel"},
-// the four orientation pairs (LAY_F = 0: free-contiguous, LAY_K = 1: K-contiguous) of one (mode, tile, vector width)
-#define CTAMD_F32X_ORIENTS(GE, BM, BN, BK, V)   \
-    CTAMD_F32X_ENTRY(GE, BM, BN, BK, 0, 0, V)   \
-    CTAMD_F32X_ENTRY(GE, BM, BN, BK, 0, 1, V)   \
-    CTAMD_F32X_ENTRY(GE, BM, BN, BK, 1, 0, V)   \
-    CTAMD_F32X_ENTRY(GE, BM, BN, BK, 1, 1, V)
+#define CTAMD_F32X_ORIENTS(GE, BM, BN, BK, V) CTAMD_GEN_FAMILY_ORIENTS(gett_gen_f32x_kernel, F32xCfg, GE, BM, BN, BK, V)
 
 }  // namespace ctamd

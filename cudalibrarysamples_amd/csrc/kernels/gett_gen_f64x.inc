@@ -18,20 +18,9 @@
 // LDS (gett_gen_layout.h): real data GenImage<4, 32> / GenFrag<4> — 128-byte rows, a lane reads ONE 16-byte unit (k = 4 q .. 4 q + 3 of
 // row r) and feeds element j to MFMA step j: the read pattern of the 16-bit image, and its swizzle; complex data the 8-byte image of
 // complex64 (GenImage<8, 16> / GenFrag<8>).  Static, two stages: 128 x 128 x 32 real 64 KiB, 128 x 64 x 16 complex 48 KiB.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "params.h"
-#include "launch.h"
-#include "gett_common.h"
-#include "gett_gen_layout.h"
+#include "gett_gen_common.h"
 
 namespace ctamd {
-
-typedef double y_f64x2 __attribute__((ext_vector_type(2)));
-typedef float  y_f32x2 __attribute__((ext_vector_type(2)));
 
 template <int GE_, int BM_, int BN_, int BK_, int OA_, int OB_, int V_>
 struct F64xCfg {
@@ -102,7 +91,7 @@ struct F64xOperand {
             }
             const double* src = X + (offR + offK) * (int64_t)SD;
             if constexpr (ND == 2) {
-                const y_f64x2 v = *reinterpret_cast<const y_f64x2*>(src);
+                const f64x2 v = *reinterpret_cast<const f64x2*>(src);
                 st[i][0] = v[0]; st[i][1] = v[1];
             } else {
                 st[i][0] = *src;
@@ -122,12 +111,12 @@ struct F64xOperand {
             const int row = Map::unit_row(tid, i);
             if constexpr (CPLX) {
                 if (conj) f[1] = -f[1];
-                *reinterpret_cast<y_f32x2*>(lds + Img::addr(row, kl)) = y_f32x2{f[0], f[1]};
+                *reinterpret_cast<f32x2*>(lds + Img::addr(row, kl)) = f32x2{f[0], f[1]};
             } else if constexpr (V == 1) {
                 *reinterpret_cast<float*>(lds + Img::addr(row, kl)) = f[0];
             } else if constexpr (ORIENT == 1) {
                 // two consecutive k of one row: 8 bytes inside one 16-byte unit of the image
-                *reinterpret_cast<y_f32x2*>(lds + Img::addr(row, kl)) = y_f32x2{f[0], f[1]};
+                *reinterpret_cast<f32x2*>(lds + Img::addr(row, kl)) = f32x2{f[0], f[1]};
             } else {
                 // free-contiguous unit: V rows at one k — the transposition happens here
 #pragma unroll
@@ -291,7 +280,7 @@ __global__ void __launch_bounds__(256, 2) gett_gen_f64x_kernel(const GettParams 
                     const uint32_t n = nBase + 16 * j + r;
                     if (n >= Ntot) continue;
                     const size_t e = tileOff + (size_t)m * Ntot + n;
-                    if constexpr (CPLX) reinterpret_cast<y_f32x2*>(p.partial)[e] = y_f32x2{acc[i][j].rr[t] - acc[i][j].ii[t], acc[i][j].x[t]};
+                    if constexpr (CPLX) reinterpret_cast<f32x2*>(p.partial)[e] = f32x2{acc[i][j].rr[t] - acc[i][j].ii[t], acc[i][j].x[t]};
                     else                p.partial[e] = acc[i][j].v[t];
                 }
             }
@@ -343,27 +332,12 @@ __global__ void __launch_bounds__(256, 2) gett_gen_f64x_kernel(const GettParams 
                         oRe += beRe * cRe - beIm * cIm;
                         oIm += beRe * cIm + beIm * cRe;
                     }
-                    *reinterpret_cast<y_f64x2*>(static_cast<double*>(p.D) + 2 * oD) = y_f64x2{oRe, oIm};
+                    *reinterpret_cast<f64x2*>(static_cast<double*>(p.D) + 2 * oD) = f64x2{oRe, oIm};
                 }
             }
         }
 }
 
-template <class Cfg>
-static hipError_t launch_gen_f64x(const GettParams& p, hipStream_t stream) {
-    if (p.nBlocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(gett_gen_f64x_kernel<Cfg>, dim3(p.nBlocks), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-// table entry: {bm, bn, bk, wm, wn, wk, layA, layB, threads, pf, kfast, ablation, launch, fragPartials, nt, elem, vec}
-#define CTAMD_F64X_ENTRY(GE, BM, BN, BK, OA, OB, V) \
-    {BM, BN, BK, 2, 2, 1, OA, OB, 256, 1, 0, 0, &launch_gen_f64x<F64xCfg<GE, BM, BN, BK, OA, OB, V>>, 0, 0, GE, V, "gett_gen_f64x_kernel"},
-// the four orientation pairs (LAY_F = 0: free-contiguous, LAY_K = 1: K-contiguous) of one (element, tile, vector width)
-#define CTAMD_F64X_ORIENTS(GE, BM, BN, BK, V)   \
-    CTAMD_F64X_ENTRY(GE, BM, BN, BK, 0, 0, V)   \
-    CTAMD_F64X_ENTRY(GE, BM, BN, BK, 0, 1, V)   \
-    CTAMD_F64X_ENTRY(GE, BM, BN, BK, 1, 0, V)   \
-    CTAMD_F64X_ENTRY(GE, BM, BN, BK, 1, 1, V)
+#define CTAMD_F64X_ORIENTS(GE, BM, BN, BK, V) CTAMD_GEN_FAMILY_ORIENTS(gett_gen_f64x_kernel, F64xCfg, GE, BM, BN, BK, V)
 
 }  // namespace ctamd

@@ -69,6 +69,19 @@ def _split(d):
     return d.get("splitK", 1) > 1
 
 
+def one_launch(d):
+    """the plan is ONE launch of its kernel: nothing peeled, reduced beforehand or repacked, no split-K fold"""
+    assert d["splitK"] == 1 and not any(d.get(k) for k in ("peel_launches", "lone_reduce_A", "lone_reduce_B", "repack_A", "repack_B")), d
+
+
+# M = {a, b} and N = {c, d} interleave in D (and C), so neither fuses: the mixed-radix side of the general family's row clamp and of its
+# epilogue offsets.  M = 63 and N = 45 are ragged against the 64-wide tile, k = 37 against every K-tile; two batches.  Pitch padding
+# (A, B, D, C): C's pitch differs from D's.
+UNFUSED = dict(a=9, b=7, c=5, d=9, k=37, l=2)
+UNFUSED_LONG = dict(UNFUSED, k=517)      # 17 K-tiles of 32 (33 of 16) on two output tiles: the planner splits K by itself
+UNFUSED_MODES = ("kabl", "kcdl", "acbdl")
+UNFUSED_PAD = (0, 0, 1, 3)
+
 HEADLINE = dict(a=96, b=64, c=64, d=64, e=96)
 HEAD_MODES = ("dcba", "ebcd", "ea")                     # 'abcd,dcbe->ae' in the ABI's order (fastest mode first)
 

@@ -68,10 +68,11 @@ def make_plan(env, ext, modes, compute, pad=(0, 0, 0), align=128, ws_limit=1 << 
     import guarded as gd
     ct, ops, h, torch = env
     e = lambda m: [ext[c] for c in m]   # noqa: E731
-    st = [gd.packed_strides(e(modes[i]), pad[i]) for i in range(3)]
+    # pad: pitch padding of A, B, D — and of C, when a fourth entry gives C a pitch of its own
+    st = [gd.packed_strides(e(modes[min(i, 2)]), pad[i]) for i in range(len(pad))]
     op = [ct.OP_CONJ if c else ct.OP_IDENTITY for c in conj]
     return ops.contraction_plan(h, e(modes[0]), modes[0], e(modes[1]), modes[1], e(modes[2]), modes[2], dtype=ct.C_32F, strideA=st[0], strideB=st[1],
-                                strideC=st[2], alignment=align, compute=compute, workspace_limit=ws_limit, opA=op[0], opB=op[1], opC=op[2])
+                                strideC=st[-1], strideD=st[2] if len(pad) > 3 else None, alignment=align, compute=compute, workspace_limit=ws_limit, opA=op[0], opB=op[1], opC=op[2])
 
 
 def contract(env, plan, ext, modes, A, B, C, alpha=1.0, beta=0.0, pad=(0, 0, 0), off=0, inplace=False, on_path=True):
@@ -85,7 +86,7 @@ def contract(env, plan, ext, modes, A, B, C, alpha=1.0, beta=0.0, pad=(0, 0, 0),
     pd = xc.Placed(e(modes[2]), "complex64", pad[2], off)
     pc = None
     if beta:
-        pc = pd if inplace else xc.Placed(e(modes[2]), "complex64", pad[2], off)
+        pc = pd if inplace else xc.Placed(e(modes[2]), "complex64", pad[-1], off)
         pc.set(C)
     ws = torch.full((max(plan.required_workspace, 256),), 0xFF, dtype=torch.uint8, device="cuda")
     before = ct.launch_counts()["gen"]
@@ -177,6 +178,20 @@ def test_exact_groups_pitches_split_k_and_in_place(env, force, compute):
     _exact(env, "c32x_splitk_odd", dict(m=100, n=60, k=4099), ("mk", "kn", "mn"), compute, vec=1, split=True, alpha=0.5 - 1j, beta=-0.5 + 2j, inplace=True)
     for i, (al, be) in enumerate(s):
         _exact(env, "c32x_scalars_%d" % i, dict(m=200, n=136, k=104), ("km", "nk", "mn"), compute, vec=2, alpha=al, beta=be, inplace=bool(i & 1))
+
+
+@pytest.mark.parametrize("compute", MODES)
+def test_exact_row_and_column_groups_that_do_not_fuse(env, force, compute):
+    """M and N of two modes each, interleaved in D: the mixed-radix row clamp and epilogue offsets, in ONE launch (xc.UNFUSED).  The family
+    has no switch that forces split-K: a second case with k = 517 splits by itself."""
+    def unfused(d, compute, vec, split):
+        on_c32x(d, compute, vec, split)
+        xc.one_launch(d)
+    _exact(env, "c32x_unfused", xc.UNFUSED, xc.UNFUSED_MODES, compute, vec=1, tile=64, alpha=0.5 - 1j, beta=-0.5 + 2j, pad=xc.UNFUSED_PAD,
+           conj=(False, True, True), check=unfused)
+    # the same groups with a K long enough to split by itself: the partial walk and the fold on groups that do not fuse
+    _exact(env, "c32x_unfused_splitk", xc.UNFUSED_LONG, xc.UNFUSED_MODES, compute, vec=1, split=True, tile=64, alpha=0.5 - 1j, beta=-0.5 + 2j,
+           pad=xc.UNFUSED_PAD, conj=(False, True, True))
 
 
 @pytest.mark.parametrize("compute", MODES)

@@ -47,9 +47,10 @@ def make_plan(env, ext, modes, compute, pad=(0, 0, 0), align=128, ws_limit=1 << 
     import guarded as gd
     ct, ops, h, torch = env
     e = lambda m: [ext[c] for c in m]   # noqa: E731
-    st = [gd.packed_strides(e(modes[i]), pad[i]) for i in range(3)]
+    # pad: pitch padding of A, B, D — and of C, when a fourth entry gives C a pitch of its own
+    st = [gd.packed_strides(e(modes[min(i, 2)]), pad[i]) for i in range(len(pad))]
     return ops.contraction_plan(h, e(modes[0]), modes[0], e(modes[1]), modes[1], e(modes[2]), modes[2], dtype=ct.R_32F, strideA=st[0], strideB=st[1],
-                                strideC=st[2], alignment=align, compute=compute, workspace_limit=ws_limit)
+                                strideC=st[-1], strideD=st[2] if len(pad) > 3 else None, alignment=align, compute=compute, workspace_limit=ws_limit)
 
 
 def contract(env, plan, ext, modes, A, B, C, alpha=1.0, beta=0.0, pad=(0, 0, 0), off=0, inplace=False, on_path=True):
@@ -64,7 +65,7 @@ def contract(env, plan, ext, modes, A, B, C, alpha=1.0, beta=0.0, pad=(0, 0, 0),
     pd = xc.Placed(e(modes[2]), "float32", pad[2], off)
     pc = None
     if beta:
-        pc = pd if inplace else xc.Placed(e(modes[2]), "float32", pad[2], off)
+        pc = pd if inplace else xc.Placed(e(modes[2]), "float32", pad[-1], off)
         pc.set(C)
     ws = torch.full((max(plan.required_workspace, 256),), 0xFF, dtype=torch.uint8, device="cuda")
     before = ct.launch_counts()["gen"]
@@ -148,6 +149,18 @@ def test_exact_lone_and_peeled_plans_recurse_into_the_path(env, force, compute):
         assert d.get("peel_launches", 0) >= 2 and d["family"] == 2 and d["elem"] == ELEM[compute], d
     _exact(env, "f32x_lone_A", xc.LONE, ("kji", "lk", "li"), compute, alpha=-2.0, beta=1.0, check=lone)
     _exact(env, "f32x_peeled", xc.PEEL, ("paqbrcsdte", "xpyqzrst", "abxcydze"), compute, alpha=0.5, beta=1.0, check=peeled)
+
+
+@pytest.mark.parametrize("compute", MODES)
+def test_exact_row_and_column_groups_that_do_not_fuse(env, force, compute):
+    """M and N of two modes each, interleaved in D: the mixed-radix row clamp and epilogue offsets, in ONE launch (xc.UNFUSED).  The family
+    has no switch that forces split-K: a second case with k = 517 splits by itself."""
+    def unfused(d, compute, vec, split):
+        on_f32x(d, compute, vec, split)
+        xc.one_launch(d)
+    _exact(env, "f32x_unfused", xc.UNFUSED, xc.UNFUSED_MODES, compute, vec=1, tile=64, alpha=-2.0, beta=0.5, pad=xc.UNFUSED_PAD, check=unfused)
+    # the same groups with a K long enough to split by itself: the partial walk and the fold on groups that do not fuse
+    _exact(env, "f32x_unfused_splitk", xc.UNFUSED_LONG, xc.UNFUSED_MODES, compute, vec=1, split=True, tile=64, alpha=-2.0, beta=0.5, pad=xc.UNFUSED_PAD)
 
 
 @pytest.mark.parametrize("roles", ("A_wide", "B_wide"))

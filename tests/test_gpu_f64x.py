@@ -54,10 +54,11 @@ def make_plan(env, kind, ext, modes, compute="32F", pad=(0, 0, 0), align=128, ws
     import guarded as gd
     ct, ops, h, torch = env
     e = lambda m: [ext[c] for c in m]   # noqa: E731
-    st = [gd.packed_strides(e(modes[i]), pad[i]) for i in range(3)]
+    # pad: pitch padding of A, B, D — and of C, when a fourth entry gives C a pitch of its own
+    st = [gd.packed_strides(e(modes[min(i, 2)]), pad[i]) for i in range(len(pad))]
     op = [ct.OP_CONJ if c else ct.OP_IDENTITY for c in conj]
     return ops.contraction_plan(h, e(modes[0]), modes[0], e(modes[1]), modes[1], e(modes[2]), modes[2], dtype=ct.R_64F if kind == "f64" else ct.C_64F,
-                                strideA=st[0], strideB=st[1], strideC=st[2], alignment=align, compute=compute, workspace_limit=ws_limit,
+                                strideA=st[0], strideB=st[1], strideC=st[-1], strideD=st[2] if len(pad) > 3 else None, alignment=align, compute=compute, workspace_limit=ws_limit,
                                 opA=op[0], opB=op[1], opC=op[2])
 
 
@@ -73,7 +74,7 @@ def contract(env, kind, plan, ext, modes, A, B, C, alpha=1.0, beta=0.0, pad=(0, 
     pd = xc.Placed(e(modes[2]), dt, pad[2], off)
     pc = None
     if beta:
-        pc = pd if inplace else xc.Placed(e(modes[2]), dt, pad[2], off)
+        pc = pd if inplace else xc.Placed(e(modes[2]), dt, pad[-1], off)
         pc.set(C)
     ws = torch.full((max(plan.required_workspace, 256),), 0xFF, dtype=torch.uint8, device="cuda")
     before = ct.launch_counts()["gen"]
@@ -143,7 +144,7 @@ def test_operands_are_rounded_to_fp32(env, force, kind):
 
 # ---- 2. exact, zero tolerance ---------------------------------------------------------------------------------------------------------
 def _exact(env, cid, kind, ext, modes, vec=None, split=None, tile=None, alpha=1.0, beta=0.0, pad=(0, 0, 0), off=0, align=128, inplace=False,
-           conj=(False, False, False)):
+           conj=(False, False, False), check=on_f64x):
     ct, ops, h, torch = env
     if kind == "f64":
         conj = (False, False, False)
@@ -154,7 +155,7 @@ def _exact(env, cid, kind, ext, modes, vec=None, split=None, tile=None, alpha=1.
     plan = make_plan(env, kind, ext, modes, "32F", pad, align, conj=conj)
     try:
         d = plan.describe()
-        on_f64x(d, kind, vec, split, tile)
+        check(d, kind, vec, split, tile)
         for swap in (False, True):
             A, B, C = xd.make_exact(case, swap)
             xd.check_draw(case, A, B, C, swap)
@@ -196,6 +197,20 @@ def test_exact_groups_pitches_split_k_and_in_place(env, force, kind):
     # split-K: fp32 / float2 partials folded in fp64; in place (C = D)
     _exact(env, "f64x_splitk", kind, dict(m=128, n=128, k=65536), ("km", "kn", "mn"), vec=2, split=True, alpha=-2.0, beta=1.0, conj=(True, True, True))
     _exact(env, "f64x_splitk_odd", kind, dict(m=100, n=60, k=4099), ("mk", "kn", "mn"), vec=1, split=True, alpha=0.5, beta=-0.5, inplace=True)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_exact_row_and_column_groups_that_do_not_fuse(env, force, kind):
+    """M and N of two modes each, interleaved in D: the mixed-radix row clamp and epilogue offsets, in ONE launch (xc.UNFUSED).  The family
+    has no switch that forces split-K: a second case with k = 517 splits by itself."""
+    def unfused(d, kind, vec, split, tile):
+        on_f64x(d, kind, vec, split, tile)
+        xc.one_launch(d)
+    _exact(env, "f64x_unfused", kind, xc.UNFUSED, xc.UNFUSED_MODES, vec=1, tile="small", alpha=-2.0, beta=0.5, pad=xc.UNFUSED_PAD, conj=(False, True, True),
+           check=unfused)
+    # the same groups with a K long enough to split by itself: the partial walk and the fold on groups that do not fuse
+    _exact(env, "f64x_unfused_splitk", kind, xc.UNFUSED_LONG, xc.UNFUSED_MODES, vec=1, split=True, tile="small", alpha=-2.0, beta=0.5, pad=xc.UNFUSED_PAD,
+           conj=(False, True, True))
 
 
 @pytest.mark.parametrize("kind", KINDS)
