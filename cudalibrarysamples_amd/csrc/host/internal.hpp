@@ -2,6 +2,8 @@
 #pragma once
 #include <atomic>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -198,7 +200,7 @@ cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t 
                                 ReducePlan& plan, std::string* why);
 
 // Raised while the pairwise plans of a trinary or a block-sparse contraction are made or priced: under COMPUTE_DESC_32F on fp64 /
-// complex128 data those keep the fp64 kernels (f64x_decide, api.cpp), and the plan memo stands aside for them
+// complex128 data those keep the fp64 kernels (f64x_decide, contraction_route.cpp), and the plan memo stands aside for them
 extern thread_local int t_f64xOff;
 struct F64xOffScope { F64xOffScope() { ++t_f64xOff; } ~F64xOffScope() { --t_f64xOff; } };
 cutensorStatus_t blocksparse_estimate(cutensorHandle_t handle, const cutensorOperationDescriptor& desc, uint64_t* ws);
@@ -353,3 +355,76 @@ struct cutensorHandle {
     struct PendingMeasurement { std::string key; int kernel; uint32_t splitK; hipEvent_t e0, e1; };
     std::vector<PendingMeasurement> pending;   // cutensorContract calls of tuning plans whose events were not read yet
 };
+
+// ---- contraction routing (contraction_route.cpp) -----------------------------------------------------------------------------
+namespace ctamd {
+
+inline int log_level() {
+    static int lvl = [] {
+        const char* e = std::getenv("CUTENSOR_LOG_LEVEL");   // contraction_jit.cu:142 hints at this knob
+        return e ? std::atoi(e) : 0;
+    }();
+    return lvl;
+}
+#define CT_LOG(...) do { if (log_level() > 0) { std::fprintf(stderr, "[cutensor-amd] " __VA_ARGS__); std::fputc('\n', stderr); } } while (0)
+
+// pieces of the workspace start at multiples of 256 bytes
+constexpr uint64_t align256(uint64_t bytes) { return (bytes + 255) & ~255ull; }
+// Two-step plans (PlanKind::LoneReduce / Repack) and their estimate: A's temporary at the head of the workspace, B's at offB, the
+// sub-plans' own workspace from offW on
+struct TwoStepLayout {
+    const uint64_t offB, offW;
+    TwoStepLayout(uint64_t bytesA, uint64_t bytesB) : offB(align256(bytesA)), offW(offB + align256(bytesB)) {}
+};
+
+// the caller names a candidate of the ranked list (CUTENSOR_ALGO >= 0 or a kernel rank): it gets that candidate
+inline bool names_candidate(const cutensorPlanPreference& pr) { return (int)pr.algo >= 0 || pr.kernelRank > 0; }
+// ... or asks for a measured choice among the candidates (CUTENSOR_ALGO_DEFAULT_PATIENT, incremental autotuning)
+inline bool names_candidate_or_tunes(const cutensorPlanPreference& pr) { return names_candidate(pr) || pr.algo == CUTENSOR_ALGO_DEFAULT_PATIENT || pr.autotune == CUTENSOR_AUTOTUNE_MODE_INCREMENTAL; }
+
+// the kernel table a ContractionChoice::kernel of `family` indexes
+const GettKernelInfo* kernel_table(int family, int* count);
+// ... and the entry itself; nullptr when `kernel` is not an index into that table
+const GettKernelInfo* kernel_info(int family, int kernel);
+
+// What cutensorCreatePlan was asked for.  cutensorEstimateWorkspaceSize builds the same request for a contraction, with the cap of its
+// workspace preference as the limit.
+struct PlanRequest {
+    cutensorHandle*                    handle;
+    const cutensorOperationDescriptor& desc;
+    cutensorPlanPreference_t           pref;      // as the caller passed it (may be null): what sub-plans are created with
+    const cutensorPlanPreference&      pr;        // the same with the defaults filled in
+    uint64_t                           wsLimit;
+};
+inline bool accumulates_in_fp64(const cutensorOperationDescriptor& d) { return d.compute && d.compute->id == 5; }   // COMPUTE_DESC_64F
+bool plan_env_override();
+
+// (split_lone_modes and plan_repack: the first steps — reductions or permuted copies of A / B — and the contraction on their results)
+struct TwoStepSplit {
+    cutensorOperationDescriptor inner, stepA, stepB;
+    bool hasA = false, hasB = false;
+    uint64_t bytesA = 0, bytesB = 0;       // packed sizes of the temporaries
+    int64_t summedA = 1, summedB = 1;      // lone modes: elements summed into each element of a temporary
+};
+bool split_lone_modes(const cutensorOperationDescriptor& desc, TwoStepSplit& out);
+int f64x_elem_of(const cutensorOperationDescriptor& d);
+extern thread_local bool t_inRepack;
+struct RepackScope { bool prev; RepackScope() : prev(t_inRepack) { t_inRepack = true; } ~RepackScope() { t_inRepack = prev; } };
+// The ranked candidates of a contraction the tiled kernels can describe, and what its repack route needs to know about them
+struct TiledRoute {
+    bool mfmaPath = false, h16Path = false, genPath = false;   // fp32 families / aligned 16-bit family / general MFMA family (h16Path implies genPath)
+    std::vector<ContractionChoice> ch;                         // best first; empty: the general family or the simple kernel
+    double tDirectUs = 0.0;                                    // > 0: fp32 / fp64 / complex64 off their fast kernels — what the plan on the operands as they lie costs
+    std::vector<std::string> notes;                            // the plan lines of the compute-descriptor decisions, for the builder to log
+    int family() const { return mfmaPath ? 0 : h16Path ? 1 : 2; }
+};
+// the routes in the order they are tried (contraction_route.cpp); each says whether it applies and returns what the builder and the
+// estimate need
+bool route_peeled(const PlanRequest& rq, const ContractionView& v, cutensorOperationDescriptor& inner, std::vector<PeelMode>& peel);
+bool route_mode_table(const PlanRequest& rq, ContractionView& v, bool accumulate64);
+TiledRoute rank_tiled_candidates(const PlanRequest& rq, const ContractionView& v, bool accumulate64);
+bool route_repack(const PlanRequest& rq, const ContractionView& v, const TiledRoute& r, TwoStepSplit& rs);
+void route_tiled(const PlanRequest& rq, const ContractionView& v, TiledRoute& r);
+cutensorStatus_t estimate_contraction(const PlanRequest& rq, cutensorWorksizePreference_t workspacePref, uint64_t* estimate);
+
+}  // namespace ctamd

@@ -574,7 +574,7 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     if (sweep && h16_k_tiles(v) >= (1ull << 30)) return false;     // (GettParams::ragged carries the padded tile count in 30 bits)
     // sweeps that fill less than 45 % of their K-tiles ('abcd,dcbe->ae' with d = 16: a quarter) are no faster than the general family on its
     // 16-byte lanes (measured, profiles/r06zz6_*: d = 40, 62 %: 543 against 411 TFLOP/s; d = 16, 25 %: below its 360) — cutensorCreatePlan
-    // then looks at copying an operand so that the contracted modes fuse (api.cpp plan_repack), else the general family takes it
+    // then looks at copying an operand so that the contracted modes fuse (contraction_route.cpp plan_repack), else the general family takes it
     if (sweep && h16_sweep_fill(v) < 0.45 && !CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES")) return false;
     const bool ragged = h16_needs_rag(v);         // the candidates are the kernels that have a RAG instantiation
     // The 16-bit kernels address an operand with 32-bit byte offsets relative to a 64-bit base that moves with the workgroup
@@ -896,7 +896,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     return true;
 }
 
-// The estimate on which f64x_decide (api.cpp) compares an fp64 / complex128 plan of this family with its single-precision twin: ONE
+// The estimate on which f64x_decide (contraction_route.cpp) compares an fp64 / complex128 plan of this family with its single-precision twin: ONE
 // formula for both sides, each at its measured rate.  Waves of workgroups x the tile's flops / (the element's MFMA rate x its measured
 // efficiency: kF64GenEff for the fp64 kernels, kF64xEffReal / kF64xEffCplx for the fp32-rate ones), never below what moving the operands
 // and the output once at 4 TB/s costs, + 2 us for the launch.  (ContractionChoice::estimateUs of an fp64 plan stays the figure for logs
@@ -918,7 +918,7 @@ double gen_f64_measured_estimate_us(const ContractionView& v, const ContractionC
     return std::max(tCompute, bytes / 4.0e12 * 1e6) + 2.0;
 }
 
-// The same for complex64 data: what f32x_decide (api.cpp) compares a complex64 plan of this family (gett_gen_kernel<GEN_C32>) with its
+// The same for complex64 data: what f32x_decide (contraction_route.cpp) compares a complex64 plan of this family (gett_gen_kernel<GEN_C32>) with its
 // reduced-precision twin (gett_gen_c32x_kernel) on.  ONE formula for both sides, each at its measured rate: 8 real flops per complex
 // multiply-add on the fp32 MFMA x kC32GenEff, or on the 16-bit MFMA (a third of it under TF32) x kC32xEffX1 / kC32xEffX3; never below what
 // moving the operands and the output once at 4 TB/s costs; + 2 us for the launch.  Negative: `c` is not such a plan.

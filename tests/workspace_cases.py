@@ -202,6 +202,60 @@ CASES = [
 
 NO_HOOKS = [c.id for c in CASES if not c.env]
 
+# ---- planner-only corners of the estimate (tests/test_workspace_contract_cpu.py; they add nothing on the device, so not in CASES) ----
+# Problems on which the estimate once took another route than the plan: COMPUTE_DESC_64F on fp32 / complex64 data (the plan runs on the
+# simple / the mode-table kernel and takes no workspace), and a caller who names a candidate (such a plan is never repacked).  `est`,
+# `req` and the path are those of the plan created at the preference's cap (the same at DEFAULT and at MAX).
+T3_BIG = dict(i=2000, l=1360, j=16, k=72)               # 'ijk,lkj->il' at a size where copying B first pays for every data type
+
+
+def _kname(name):
+    return lambda d: d.get("kname") == name and not d.any("repack_A") and not d.any("repack_B")
+
+
+class Corner:
+    def __init__(self, id, dtype, ext, modes, expect, est, req, **plan_kw):
+        self.id, self.dtype, self.ext, self.modes, self.expect, self.est, self.req, self.plan_kw = id, dtype, ext, modes, expect, est, req, plan_kw
+
+    def __repr__(self):
+        return self.id
+
+
+_BIG = ("kji", "jkl", "li")
+CORNERS = [
+    Corner("f32_odd_compute64", "float32", ODD, ("mk", "kn", "mn"), _kname("gett_simple_kernel"), 0, 0, compute="64F"),
+    Corner("f32_headline_compute64", "float32", HEAD, ("dcba", "ebcd", "ea"), _kname("gett_simple_kernel"), 0, 0, compute="64F"),
+    Corner("c64_odd_compute64", "complex64", ODD, ("mk", "kn", "mn"), _kname("gett_wide_kernel"), 0, 0, compute="64F"),
+    # the caller names candidate 0: the operands as they lie
+    Corner("bf16_big_algo0", "bfloat16", T3_BIG, _BIG, _kname("gett_gen_kernel"), 0, 0, algo=0),
+    Corner("f64_big_algo0", "float64", T3_BIG, _BIG, _kname("gett_gen_kernel"), 0, 0, algo=0),
+    # fp32: the best four of the direct list, which holds what candidate 0 (splitK 2) and candidate 1 (splitK 4) need
+    Corner("f32_big_algo0", "float32", T3_BIG, _BIG, _kname("gett_f32_kernel"), 43520000, 21760000, algo=0),
+    Corner("f32_big_rank1", "float32", T3_BIG, _BIG, _kname("gett_f32_kernel"), 43520000, 43520000, kernel_rank=1),
+    # the same shapes without a named candidate: B copied first; bf16 / fp64 need the temporary alone, fp32 keeps the best-four bound of
+    # the inner problem's list on top of it
+    Corner("bf16_big", "bfloat16", T3_BIG, _BIG, _repack(0, 1, _family(1, "gett_h16w4m4_kernel", False)), 3133440, 3133440),
+    Corner("f64_big", "float64", T3_BIG, _BIG, _repack(0, 1, _family(2, "gett_gen_kernel", False)), 12533760, 12533760),
+    Corner("f32_big", "float32", T3_BIG, _BIG, _repack(0, 1, _family(0, "gett_f32_stream_kernel", False)), 28026880, 6266880),
+]
+
+
+def corner_contract(ct, ops, corner):
+    """estimate, required workspace and path of a corner at the DEFAULT and the MAX cap, and the agreement rule of plan_contract"""
+    dt = {"bfloat16": ct.R_16BF, "float32": ct.R_32F, "float64": ct.R_64F, "complex64": ct.C_32F}[corner.dtype]
+    e = lambda m: [corner.ext[c] for c in m]   # noqa: E731
+    m = corner.modes
+    h = ops.Handle()
+    for name, pref in (("DEFAULT", ct.WORKSPACE_DEFAULT), ("MAX", ct.WORKSPACE_MAX)):
+        p = ops.contraction_plan(h, e(m[0]), m[0], e(m[1]), m[1], e(m[2]), m[2], dtype=dt, workspace_pref=pref, workspace_limit=CAPS[name],
+                                 **corner.plan_kw)
+        try:
+            d = check_agreement(ct, "%s %s" % (corner.id, name), p, p.workspace_estimate)
+            assert corner.expect(d), "%s is off its path: %s" % (corner.id, d)
+            assert (p.workspace_estimate, p.required_workspace) == (corner.est, corner.req), (corner.id, name, p.workspace_estimate, p.required_workspace)
+        finally:
+            p.destroy()
+
 
 @contextmanager
 def hook_env(case):
@@ -411,9 +465,40 @@ def _check_limits(ct, ops, h, case, est_min, limits):
             p.destroy()
 
 
+# The workspace limit cutensorEstimateWorkspaceSize routes a problem at, per preference: `cap` in cutensorEstimateWorkspaceSize
+# (cudalibrarysamples_amd/csrc/host/api.cpp); WORKSPACE_MIN routes nothing
+CAPS = {"DEFAULT": 1 << 30, "MAX": 4 << 30}
+
+
+def _has_family0(pairs):
+    """a kernel of family 0 (the fp32 ranked list) anywhere in a plan's description, top level or inner"""
+    for item in pairs:
+        if isinstance(item, tuple):
+            if item[0] == "family" and item[1] == 0:
+                return True
+            item = item[1]
+        if isinstance(item, list) and _has_family0(item):
+            return True
+    return False
+
+
+def check_agreement(ct, what, plan_at_cap, estimate):
+    """The estimate is the route cutensorCreatePlan takes at the preference's cap, added up: it equals what the plan created at the cap
+    requires.  The one exception is the library's policy for the fp32 ranked list (family 0): the estimate is the largest need among
+    its best four candidates, so it bounds the requirement from above."""
+    d = describe(ct, plan_at_cap)
+    req = plan_at_cap.required_workspace
+    if _has_family0(d.pairs):
+        assert estimate >= req, "%s: estimate %d below what the plan at the cap requires (%d): %s" % (what, estimate, req, d)
+    else:
+        assert estimate == req, "%s: estimate %d, the plan at the cap requires %d: %s" % (what, estimate, req, d)
+    return d
+
+
 def plan_contract(ct, ops, case):
     """a plan at each preference's estimate requires at most that estimate; MIN <= DEFAULT <= MAX; at any limit a plan fits or is
-    refused with INSUFFICIENT_WORKSPACE, and only below estimate(MIN)"""
+    refused with INSUFFICIENT_WORKSPACE, and only below estimate(MIN); the DEFAULT and MAX estimates agree with the plan created at
+    the preference's cap (check_agreement)"""
     h = ops.Handle()
     est = {}
     for name, pref in (("MIN", ct.WORKSPACE_MIN), ("DEFAULT", ct.WORKSPACE_DEFAULT), ("MAX", ct.WORKSPACE_MAX)):
@@ -425,6 +510,11 @@ def plan_contract(ct, ops, case):
             req = p.required_workspace
         est[name] = p.workspace_estimate
         p.destroy()
+        if name in CAPS:
+            p, st = _plan_or_status(ct, ops, h, case, workspace_pref=pref, workspace_limit=CAPS[name])
+            assert p is not None, "%s: no plan at the %s cap (status %d)" % (case.id, name, st)
+            check_agreement(ct, "%s %s" % (case.id, name), p, est[name])
+            p.destroy()
     assert est["MIN"] <= est["DEFAULT"] <= est["MAX"], (case.id, est)
     if case.kind in ("permutation", "binary", "trinary"):
         assert est["MAX"] == 0 and req == 0, (case.id, est, req)
