@@ -46,8 +46,8 @@ bool valid_compute(cutensorComputeDescriptor_t c) { return c >= &kCompute[0] && 
 
 
 bool supported_dtype(hipDataType t) {
-    // complex data: contractions (general MFMA family / mode-table kernel), reductions, permutations and the binary element-wise
-    // form (ADD / MUL); the trinary element-wise planner answers NOT_SUPPORTED for it
+    // complex data: contractions (general MFMA family / mode-table kernel), reductions, permutations and the binary and trinary
+    // element-wise forms (ADD / MUL, operand operators IDENTITY / CONJ; the trinary form on kernels/elementwise_trinary_cplx.hip)
     return t == HIP_R_32F || t == HIP_R_64F || t == HIP_R_16F || t == HIP_R_16BF || t == HIP_C_32F || t == HIP_C_64F;
 }
 
@@ -1654,6 +1654,21 @@ static hipError_t run_elementwise(const EwPlan& ew, hipDataType dtype, double a,
     return launch_elementwise(p, variant, (int)dtype, stream);
 }
 
+// One launch of a complex trinary plan's pass (kernels/elementwise_trinary_cplx.hip): A on the tile path, X the second permuted operand
+// or nullptr, E the operand with D's strides or nullptr; complex scalars as (re, im).  C is dropped as run_elementwise drops it.
+struct CxScalar { double re, im; };
+static hipError_t run_trinary_cplx(const EwPlan& ew, hipDataType dtype, CxScalar a, const void* A, CxScalar x, const void* X, CxScalar d,
+                                   const void* E, CxScalar g, const void* C, void* D, hipStream_t stream) {
+    Ew2DParams p = ew.p;
+    p.A = A; p.X = X; p.E = E; p.D = D;
+    p.C = (ew.usesC && (g.re != 0.0 || g.im != 0.0 || (p.opAC != 0 && p.opAC != CUTENSOR_OP_ADD))) ? C : nullptr;
+    p.alpha = (float)a.re; p.alpha64 = a.re; p.alphaIm = a.im;
+    p.gamma = (float)g.re; p.gamma64 = g.re; p.gammaIm = g.im;
+    p.xi = (float)x.re; p.xi64 = x.re;
+    p.delta = (float)d.re; p.delta64 = d.re;
+    return launch_elementwise_trinary_cplx(p, x.im, d.im, ew.conjX, ew.conjE, ew.variant, (int)dtype, stream);
+}
+
 // reduction.cu:219-222, einsum.cu:369-372
 cutensorStatus_t cutensorReduce(const cutensorHandle_t handle, const cutensorPlan_t plan, const void* alpha,
                                 const void* A, const void* beta, const void* C, void* D, void* workspace,
@@ -1735,7 +1750,28 @@ cutensorStatus_t cutensorElementwiseTrinaryExecute(const cutensorHandle_t handle
                  g = scalar_as_double(gamma, plan->scalarType);
     const EwTrinaryPlan& t = plan->ew3;
     hipError_t err = hipSuccess;
-    if (t.bothPermuted) {
+    if (plan->dtype == HIP_C_32F || plan->dtype == HIP_C_64F) {
+        // complex data: the same forms, every launch that carries an E or X operand on the complex trinary kernels
+        const CxScalar ca{a, scalar_imag(alpha, plan->scalarType)}, cb{b, scalar_imag(beta, plan->scalarType)},
+                       cg{g, scalar_imag(gamma, plan->scalarType)}, none{0.0, 0.0}, one{1.0, 0.0};
+        if (t.bothPermuted) {
+            err = run_trinary_cplx(t.last, plan->dtype, ca, A, cb, B, none, nullptr, cg, C, D, stream);
+        } else if (t.twoPass) {
+            const uintptr_t c = reinterpret_cast<uintptr_t>(C), d = reinterpret_cast<uintptr_t>(D);
+            const bool readsC = t.last.usesC && (cg.re != 0.0 || cg.im != 0.0 || (t.last.p.opAC != 0 && t.last.p.opAC != CUTENSOR_OP_ADD));
+            if (readsC && c < d + t.spanD && d < c + t.spanC) {      // C overlaps D: the single gather launch, as for real data
+                if (!t.hasGather) return CUTENSOR_STATUS_NOT_SUPPORTED;
+                err = run_trinary_cplx(t.gather, plan->dtype, ca, A, cb, B, none, nullptr, cg, C, D, stream);
+            } else {
+                err = run_elementwise(t.first, plan->dtype, ca.re, A, 0.0, nullptr, D, stream, nullptr, 0.0, ca.im);          // D = alpha cj(perm A)
+                if (err == hipSuccess) err = run_trinary_cplx(t.last, plan->dtype, cb, B, none, nullptr, one, D, cg, C, D, stream);   // in place, E = D
+            }
+        } else if (t.swapAB) {
+            err = run_trinary_cplx(t.last, plan->dtype, ca, A, none, nullptr, cb, B, cg, C, D, stream);   // E = B
+        } else {
+            err = run_trinary_cplx(t.last, plan->dtype, cb, B, none, nullptr, ca, A, cg, C, D, stream);   // E = A
+        }
+    } else if (t.bothPermuted) {
         Ew2DParams q = t.last.p;
         q.A = A; q.X = B; q.D = D; q.E = nullptr;
         q.C = (t.last.usesC && (g != 0.0 || (q.opAC != 0 && q.opAC != CUTENSOR_OP_ADD))) ? C : nullptr;
@@ -1982,6 +2018,12 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
         const int32_t uA = t.bothPermuted ? q.unA : t.twoPass ? t.first.p.unA : t.swapAB ? q.unA : q.unE;
         const int32_t uB = t.bothPermuted ? q.unX : t.twoPass ? q.unA : t.swapAB ? q.unE : q.unA;
         n = describe_unary(buf, len, n, uA, uB, q.unC);
+        // complex plans: each operand's conjugation, read back the same way
+        if ((plan->dtype == HIP_C_32F || plan->dtype == HIP_C_64F) && n > 1 && (size_t)n < len && buf[n - 1] == '}') {
+            const int cA = t.bothPermuted ? q.conjA : t.twoPass ? t.first.p.conjA : t.swapAB ? q.conjA : t.last.conjE;
+            const int cB = t.bothPermuted ? t.last.conjX : t.twoPass ? q.conjA : t.swapAB ? t.last.conjE : q.conjA;
+            n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"conj\":[%d,%d,%d]}", cA, cB, (int)q.conjC);
+        }
     } else {
         const EwPlan& e = (plan->kind == OpKind::Reduction) ? plan->red.perm : plan->ew;
         n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u,\"order\":%u}",

@@ -169,6 +169,9 @@ struct EwPlan {
     // data types of A and of D (and C): they differ in a converting plan, which runs on kernels/elementwise_convert.hip
     hipDataType dtypeA = HIP_R_32F, dtypeD = HIP_R_32F;
     bool converts() const { return dtypeA != dtypeD; }
+    // complex trinary plans (kernels/elementwise_trinary_cplx.hip): conjugation of the second permuted operand X and of the operand that
+    // rides along as E — Ew2DParams, the argument block of the other kernels, has no field for either
+    int32_t    conjX = 0, conjE = 0;
 };
 // cutensorElementwiseTrinaryExecute: D = opABC(opAB(alpha A, beta B), gamma C) as one or two passes of the
 // element-wise kernels (plan_elementwise_trinary)
@@ -193,7 +196,8 @@ struct ReducePlan {
     EwPlan       perm;
 };
 
-// allowWide = false: never the tiled kernels of 8- / 16-byte elements (the trinary planner: they take no E / X operand)
+// allowWide = false: never the tiled kernels of 8- / 16-byte elements (the trinary planner on real data: they take no E / X operand; on
+// complex data its passes run on kernels of their own that do, and it allows them)
 cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan& plan, std::string* why, bool allowWide = true);
 cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op, EwTrinaryPlan& plan, std::string* why);
 cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t wsLimit, int numCUs,

@@ -100,9 +100,9 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     const bool usesX = op.kind == OpKind::ElementwiseBinary && op.B.present;
     if (usesX && (op.B.desc.dtype != D.desc.dtype || dup_labels(op.B.modes))) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "second permuted operand");
     // complex data (python/einsum.h:326-343 routes a unary einsum on complex tensors here through cutensorCreateReduction):
-    // one permuted operand, combiner ADD or MUL, conjugation of A / C — the (re, im)-pair form of the generic kernel
+    // combiner ADD or MUL, conjugation of every operand — the (re, im)-pair form of the generic kernel; a second permuted operand (and an
+    // E operand, attached at run time) only on the kernels of elementwise_trinary_cplx.hip, which the trinary planner's passes run on
     const bool cplx = D.desc.dtype == HIP_C_32F || D.desc.dtype == HIP_C_64F;
-    if (cplx && usesX) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "complex element-wise trinary operations");
     if (cplx && op.kind == OpKind::ElementwiseBinary && op.opReduce != CUTENSOR_OP_ADD && op.opReduce != CUTENSOR_OP_MUL)
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "MAX / MIN are not defined on complex data");
     if (dup_labels(A.modes) || dup_labels(D.modes) || (usesC && dup_labels(C.modes)))
@@ -129,7 +129,7 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     if (const char* r = unary_refusal(A.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     if (usesC) if (const char* r = unary_refusal(C.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     if (usesX) {
-        if (op.B.op == CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "conjugation of the second permuted operand");
+        if (op.B.op == CUTENSOR_OP_CONJ && !cplx) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "conjugation of the second permuted operand");
         if (const char* r = unary_refusal(op.B.op, D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
     }
     for (int32_t l : A.modes)
@@ -204,6 +204,7 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     p.unA = unary_code(A.op);
     p.unC = usesC ? unary_code(C.op) : 0;
     p.unX = usesX ? unary_code(op.B.op) : 0;
+    plan.conjX = (cplx && usesX && op.B.op == CUTENSOR_OP_CONJ) ? 1 : 0;
     std::vector<EwMode> rest;
     int i1 = -1;
     if (!modes.empty()) {
@@ -272,8 +273,9 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
     // vector paths: fp32 (4-element lanes) and bf16 / fp16 (8-element lanes); "mult4" = multiple of the lane width
     const bool h16 = D.desc.dtype == HIP_R_16BF || D.desc.dtype == HIP_R_16F;
     // 8- / 16-byte elements (round 6; elementwise.hip ew_transpose_wide_kernel / ew_rowcopy_wide_kernel): permutations and binary
-    // operations on fp64 / complex64 / complex128 — a 16-byte lane holds 2 / 2 / 1 elements; never with a trinary operand (E / X)
-    const bool wide = allowWide && !usesX && (D.desc.dtype == HIP_R_64F || cplx);
+    // operations on fp64 / complex64 / complex128 — a 16-byte lane holds 2 / 2 / 1 elements; with a trinary operand (E / X) on complex
+    // data only, where the trinary planner allows them for its passes (elementwise_trinary_cplx.hip: the same tiles and lane conditions)
+    const bool wide = allowWide && (!usesX || cplx) && (D.desc.dtype == HIP_R_64F || cplx);
     const bool f32 = D.desc.dtype == HIP_R_32F || (h16 && !usesX) || wide;
     const int64_t vec = wide ? 16 / (int64_t)dtype_size(D.desc.dtype) : h16 ? 8 : 4;
     const bool aligned = (A.desc.alignment % 16 == 0) && (D.desc.alignment % 16 == 0) &&
@@ -303,6 +305,10 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
                 // fp64 / complex64: 128 x 32 elements (1-KiB written, 256-B read segments); complex128: 64 x 32 (1 KiB / 512 B)
                 t0 = D.desc.dtype == HIP_C_64F ? 64 : 128;
                 t1 = 32;
+                // complex64 with a second permuted operand (the two-tile trinary form, elementwise_trinary_cplx.hip): 64 x 64 — tile0 halved, 512-B
+                // read segments on BOTH strided operands, and two tiles of 64 x (64 + 2) x 8 bytes are exactly the real two-tile form's LDS
+                // (400 x 200 x 300: 2.99 -> 3.63 TB/s, 512 x 256 x 256: 3.92 -> 4.03 against 128 x 32; profiles/cplx_trinary_tile_ab.jsonl)
+                if (usesX && D.desc.dtype == HIP_C_32F) { t0 = 64; t1 = 64; }
             } else if (h16 && p.E1 % 64 == 0) {
                 // 16-bit: the wide kernel handles full tiles only (T0 x T1 elements: 512-B / 256-B written, 256-B / 128-B read segments)
                 if (p.E0 % 256 == 0) t0 = 256;
@@ -421,23 +427,35 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
 //   * an operand of A / B that already has D's layout rides along as E: one pass, 4 |D| bytes;
 //   * otherwise pass 1 writes D = alpha perm(A) and pass 2 combines in place with beta perm(B) and gamma C:
 //     6 |D| bytes (the combiners ADD / MUL / MAX / MIN commute, so the order of A and B is free).
-cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op, EwTrinaryPlan& plan, std::string* why) {
+//
+// Complex data (complex64 / complex128 throughout): the same three forms and the same in-place fallback on the kernels of
+// kernels/elementwise_trinary_cplx.hip — the tiled kernels of 16-byte lanes where their lane conditions hold for every operand of the pass
+// (allowWide), the element-gather kernel otherwise; pass 1 of the two-pass form is an ordinary complex permutation.  Operand operators:
+// IDENTITY and CONJ, each read back by ctamdDescribePlan from the role its form gave the operand; combiners: ADD and MUL.
+cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& opIn, EwTrinaryPlan& plan, std::string* why) {
     auto fail = [&](cutensorStatus_t st, const char* msg) {
         if (why) *why = msg;
         return st;
     };
     auto ok_op = [](cutensorOperator_t o) { return o == CUTENSOR_OP_ADD || o == CUTENSOR_OP_MUL || o == CUTENSOR_OP_MAX || o == CUTENSOR_OP_MIN; };
-    if (!ok_op(op.opAB) || !ok_op(op.opReduce)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "binary operator");
-    if (op.D.desc.dtype == HIP_C_32F || op.D.desc.dtype == HIP_C_64F) {
-        for (const TensorUse* t : {&op.A, &op.B, &op.C})
+    if (!ok_op(opIn.opAB) || !ok_op(opIn.opReduce)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "binary operator");
+    const bool cplx = opIn.D.desc.dtype == HIP_C_32F || opIn.D.desc.dtype == HIP_C_64F;
+    cutensorOperationDescriptor op = opIn;
+    if (cplx) {
+        for (const TensorUse* t : {&op.A, &op.B, &op.C}) {
             if (!unary_is_plain(t->op)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, unary_refusal(t->op, op.D.desc.dtype));
-        return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "complex element-wise trinary operations");
+            if (t->desc.dtype != op.D.desc.dtype) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types");
+        }
+        for (cutensorOperator_t o : {op.opAB, op.opReduce})
+            if (o != CUTENSOR_OP_ADD && o != CUTENSOR_OP_MUL) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "MAX / MIN are not defined on complex data");
+    } else {
+        // real data: CONJ is the identity, as cutensorCreateReduction and the binary form take it — planned as the IDENTITY descriptor
+        for (TensorUse* t : {&op.A, &op.B, &op.C})
+            if (t->op == CUTENSOR_OP_CONJ) t->op = CUTENSOR_OP_IDENTITY;
     }
     // unary operators: IDENTITY and the nine of kernels/unary_op.h; each one follows its operand into whichever role the forms below give it
-    for (const TensorUse* t : {&op.A, &op.B, &op.C}) {
-        if (t->op == CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "conjugation in an element-wise trinary operation");
+    for (const TensorUse* t : {&op.A, &op.B, &op.C})
         if (const char* r = unary_refusal(t->op, op.D.desc.dtype)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, r);
-    }
     auto same_layout = [&](const TensorUse& X) {
         if (X.modes.size() != op.D.modes.size() || X.desc.dtype != op.D.desc.dtype) return false;
         for (size_t i = 0; i < op.D.modes.size(); ++i) {
@@ -467,7 +485,7 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
         both.A = op.A;            // tile path
         both.B = op.B;            // second tile (X)
         EwPlan one;
-        const bool oneOK = plan_elementwise(both, one, nullptr, false) == CUTENSOR_STATUS_SUCCESS && one.usesX;
+        const bool oneOK = plan_elementwise(both, one, nullptr, cplx) == CUTENSOR_STATUS_SUCCESS && one.usesX;
         if (oneOK && one.variant == EW_TRANSPOSE) {
             plan.twoPass = false;
             plan.bothPermuted = true;
@@ -490,16 +508,17 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op,
         cutensorOperationDescriptor first = op;
         first.kind = OpKind::Permutation;
         first.C = TensorUse{};
-        cutensorStatus_t st = plan_elementwise(first, plan.first, why, false);
+        cutensorStatus_t st = plan_elementwise(first, plan.first, why, cplx);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
         last.A = op.B;
     }
-    cutensorStatus_t st = plan_elementwise(last, plan.last, why, false);
+    cutensorStatus_t st = plan_elementwise(last, plan.last, why, cplx);
     if (st != CUTENSOR_STATUS_SUCCESS) return st;
     plan.last.p.opAB = (int32_t)op.opAB;
     plan.last.p.opAC = (int32_t)op.opReduce;
     // E: the operand with D's layout carries its own operator; the two-pass form's E is pass 1's output alpha * unA(perm A) — no operator again
     plan.last.p.unE = plan.twoPass ? 0 : unary_code(plan.swapAB ? op.B.op : op.A.op);
+    plan.last.conjE = (cplx && !plan.twoPass && (plan.swapAB ? op.B.op : op.A.op) == CUTENSOR_OP_CONJ) ? 1 : 0;
     return CUTENSOR_STATUS_SUCCESS;
 }
 

@@ -124,6 +124,11 @@ hipError_t launch_elementwise(const Ew2DParams& p, int variant, int dtype, hipSt
 // the converting kernels (elementwise_convert.hip): A of dtypeA, D and C of dtypeD — bf16 / fp16 <-> fp32 and fp32 <-> fp64; variants
 // EW_TRANSPOSE / EW_ROWCOPY / EW_GENERIC with a lane of 16 / min(sizeof A, sizeof D) elements; any other pair or variant is an error
 hipError_t launch_elementwise_convert(const Ew2DParams& p, int variant, int dtypeA, int dtypeD, hipStream_t stream);
+// the complex trinary kernels (elementwise_trinary_cplx.hip): complex64 / complex128 data with an E and / or X operand attached; variants
+// EW_TRANSPOSE / EW_ROWCOPY / EW_GENERIC.  p carries the scalars' other parts (alpha64 / alphaIm, gamma64 / gammaIm, xi64, delta64) and
+// conjA / conjC; xiIm / deltaIm / conjX / conjE are what Ew2DParams has no field for
+hipError_t launch_elementwise_trinary_cplx(const Ew2DParams& p, double xiIm, double deltaIm, int conjX, int conjE, int variant, int dtype,
+                                           hipStream_t stream);
 // D[0 .. n) = value (contiguous; the padded-permutation border fill)
 hipError_t launch_fill(void* D, uint64_t n, int dtype, double value, hipStream_t stream);
 
