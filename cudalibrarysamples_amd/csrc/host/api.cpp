@@ -82,6 +82,7 @@ std::string problem_key(const cutensorOperationDescriptor& op) {
     // a converting element-wise problem (D's / C's type differs from A's) is another problem than the same-type one of the same shapes
     if ((op.D.present && op.D.desc.dtype != op.A.desc.dtype) || (op.C.present && op.C.desc.dtype != op.A.desc.dtype))
         ss << ":d" << (int)op.D.desc.dtype << ":c" << (op.C.present ? (int)op.C.desc.dtype : -1);
+    if (op.B.present && op.B.desc.dtype != op.A.desc.dtype) ss << ":b" << (int)op.B.desc.dtype;      // a mixed fp64 x complex128 contraction
     auto put = [&](const TensorUse& u) {
         ss << '|';
         if (!u.present) return;
@@ -108,6 +109,7 @@ bool build_memo_key(const cutensorOperationDescriptor& op, const cutensorPlanPre
     k.operandsStreamed = (uint8_t)(pr.operandsStreamed != 0);
     k.kind = (uint8_t)op.kind; k.dtype = (uint8_t)op.A.desc.dtype; k.compute = (uint8_t)(op.compute ? op.compute->id : 255);
     k.scalarType = (uint8_t)op.scalarType;
+    k.dtypeB = (op.B.present && op.B.desc.dtype != op.A.desc.dtype) ? (uint32_t)op.B.desc.dtype + 1u : 0u;
     k.dtypeD = op.D.present ? (uint8_t)op.D.desc.dtype : (uint8_t)255; k.dtypeC = op.C.present ? (uint8_t)op.C.desc.dtype : (uint8_t)255;
     k.op[0] = (uint8_t)op.A.op; k.op[1] = (uint8_t)op.B.op; k.op[2] = (uint8_t)op.C.op; k.op[3] = (uint8_t)op.opReduce;
     k.present = 0;
@@ -397,7 +399,13 @@ cutensorStatus_t cutensorCreateContraction(const cutensorHandle_t handle, cutens
     if ((st = fill_use(op.C, descC, modeC, opC)) != CUTENSOR_STATUS_SUCCESS) return st;
     if ((st = fill_use(op.D, descD, modeD, CUTENSOR_OP_IDENTITY)) != CUTENSOR_STATUS_SUCCESS) return st;
     op.compute = descCompute;
-    op.scalarType = scalar_type_for(op.A.desc.dtype, descCompute);
+    // (a mixed contraction — one input R_64F, the other one, C and D C_64F — takes the scalars of its output: complex double)
+    op.scalarType = scalar_type_for(op.A.desc.dtype != op.B.desc.dtype ? op.D.desc.dtype : op.A.desc.dtype, descCompute);
+    // bytes the operation moves: every tensor at its own element size (contraction.cu:274-276)
+    auto moved_bytes = [&] {
+        return (double)dtype_size(op.A.desc.dtype) * num_elements(op.A.desc) + (double)dtype_size(op.B.desc.dtype) * num_elements(op.B.desc) +
+               (double)dtype_size(op.D.desc.dtype) * num_elements(op.D.desc);
+    };
     ContractionView v;
     std::string why;
     {
@@ -410,8 +418,7 @@ cutensorStatus_t cutensorCreateContraction(const cutensorHandle_t handle, cutens
             if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
             op.flops = 2.0 * (double)v.totL * (double)v.totM * (double)v.totN * (double)v.totK + (ls.hasA ? num_elements(op.A.desc) : 0.0) +
                        (ls.hasB ? num_elements(op.B.desc) : 0.0);
-            const double esz = (double)dtype_size(op.A.desc.dtype);
-            op.movedBytes = esz * (num_elements(op.A.desc) + num_elements(op.B.desc) + num_elements(op.D.desc));
+            op.movedBytes = moved_bytes();
             return new_op(desc, op);
         }
     }
@@ -419,8 +426,7 @@ cutensorStatus_t cutensorCreateContraction(const cutensorHandle_t handle, cutens
     if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateContraction: %s", why.c_str()); return st; }
     // contraction.cu:61 / :274-276
     op.flops = 2.0 * (double)v.totL * (double)v.totM * (double)v.totN * (double)v.totK;
-    const double es = (double)dtype_size(op.A.desc.dtype);
-    op.movedBytes = es * (num_elements(op.A.desc) + num_elements(op.B.desc) + num_elements(op.D.desc));
+    op.movedBytes = moved_bytes();
     return new_op(desc, op);
 } CTAMD_API_CATCH
 
@@ -447,6 +453,8 @@ cutensorStatus_t cutensorCreateContractionTrinary(const cutensorHandle_t handle,
     if ((st = fill_use(op.E, descE, modeE, CUTENSOR_OP_IDENTITY)) != CUTENSOR_STATUS_SUCCESS) return st;
     op.compute = descCompute;
     op.scalarType = scalar_type_for(op.A.desc.dtype, descCompute);
+    for (const TensorUse* u : {&op.B, &op.C, &op.D, &op.E})      // (the mixed fp64 x complex128 rows belong to the pairwise contraction alone)
+        if (u->desc.dtype != op.A.desc.dtype) { CT_LOG("cutensorCreateContractionTrinary: mixed data types"); return CUTENSOR_STATUS_NOT_SUPPORTED; }
     const TensorUse* in[3] = {&op.A, &op.B, &op.C};
     auto has = [](const std::vector<int32_t>& v, int32_t l) { return std::find(v.begin(), v.end(), l) != v.end(); };
     double bestCost = 0.0;
@@ -781,7 +789,8 @@ cutensorStatus_t cutensorEstimateWorkspaceSize(const cutensorHandle_t handle, co
 // the fold that matches a kernel's split-K partials: accumulator-register order (fp32 ring kernels), row-major fp32, or — general family
 // with 8- / 16-byte elements — row-major partials in the accumulator type
 static hipError_t launch_splitk_fold(int family, const GettKernelInfo& k, const SplitKReduceParams& r, hipStream_t stream) {
-    if (family == 2 && !gen_elem_f32_partials(k.elem)) return launch_gen_splitk_reduce(r, k.elem, stream);
+    // (the mixed fp64 x complex128 kernels write complex128's double2 partials: complex128's fold takes them as they are)
+    if (family == 2 && !gen_elem_f32_partials(k.elem)) return launch_gen_splitk_reduce(r, k.elem == GEN_RC64 ? (int)GEN_C64 : k.elem, stream);
     return k.fragPartials ? launch_splitk_reduce_frag(r, stream) : launch_splitk_reduce(r, stream);
 }
 
@@ -798,8 +807,7 @@ struct DeviceScratch {
     // A, B, D of the operation's own spans and a workspace; A and B hold finite, non-trivial data: 0x3c3c3c3c = 0.0115f (0x3c3c: 0.0115 in
     // bf16, 1.06 in fp16)
     bool alloc(const cutensorOperationDescriptor& op, size_t wsBytes) {
-        const size_t es = dtype_size(op.A.desc.dtype);
-        auto span = [&](const cutensorTensorDescriptor& d) { return (size_t)d.numElementsSpanned() * es; };
+        auto span = [&](const cutensorTensorDescriptor& d) { return (size_t)d.numElementsSpanned() * dtype_size(d.dtype); };
         if (hipMalloc(&A, span(op.A.desc)) != hipSuccess || hipMalloc(&B, span(op.B.desc)) != hipSuccess || hipMalloc(&D, span(op.D.desc)) != hipSuccess ||
             (wsBytes && hipMalloc(&W, wsBytes) != hipSuccess)) return false;
         (void)hipMemset(A, 0x3c, span(op.A.desc));
@@ -1093,6 +1101,7 @@ static Built build_mode_table(const PlanRequest& rq, cutensorPlan& pl) {
     pl.wide.outTotal = outTotal;
     pl.wide.kTotal = (uint32_t)v.totK;
     set_conjugation(rq.desc, v.swapped, pl.wide.conjA, pl.wide.conjB, pl.wide.conjC);
+    pl.wide.realOperand = v.realSide + 1;      // a mixed fp64 x complex128 contraction: the kernel reads that input as doubles
     if (tab.empty()) tab.push_back(WideMode{make_fastdiv(1), 0, 0, 0, 0});
     // The table goes to device memory HERE when the handle has a device — on the handle's device, outside any stream capture, so that
     // cutensorContract neither allocates nor synchronises (it may be called while a graph is being captured).  Handles without a
@@ -1371,6 +1380,9 @@ cutensorStatus_t cutensorCreatePlan(const cutensorHandle_t handle, cutensorPlan_
     if (pl == nullptr) return CUTENSOR_STATUS_ALLOC_FAILED;
     pl->kind = desc->kind;
     pl->dtype = desc->A.desc.dtype;
+    pl->dtypeA = desc->A.desc.dtype;
+    pl->dtypeB = desc->B.present ? desc->B.desc.dtype : desc->A.desc.dtype;
+    if (desc->kind == OpKind::Contraction && pl->dtypeB != pl->dtypeA) pl->dtype = desc->D.desc.dtype;      // mixed fp64 x complex128: the output's
     pl->scalarType = desc->scalarType;
     pl->alignA = desc->A.desc.alignment;
     pl->alignB = desc->B.present ? desc->B.desc.alignment : 0;
@@ -1438,7 +1450,8 @@ static cutensorStatus_t run_two_step(const cutensorHandle_t handle, const cutens
 static cutensorStatus_t run_peeled(const cutensorHandle_t handle, const cutensorPlan& plan, const void* alpha, const void* A, const void* B,
                                    const void* beta, const void* C, void* D, void* workspace, uint64_t workspaceSize, cudaStream_t stream) {
     if (!plan.sub1) return CUTENSOR_STATUS_INVALID_VALUE;
-    const int64_t es = (int64_t)dtype_size(plan.dtype);
+    const int64_t es = (int64_t)dtype_size(plan.dtype);      // C and D; A and B at their own element size (a mixed plan's real input: 8 bytes)
+    const int64_t esA = (int64_t)dtype_size(plan.dtypeA), esB = (int64_t)dtype_size(plan.dtypeB);
     const void* one = scalar_constant(plan.scalarType, true);
     const size_t n = plan.peel.size();
     std::vector<int64_t> digit(n, 0);
@@ -1453,8 +1466,8 @@ static cutensorStatus_t run_peeled(const cutensorHandle_t handle, const cutensor
         char* d = static_cast<char*>(D) + oD * es;
         const char* c = first ? (C ? static_cast<const char*>(C) + oC * es : nullptr) : d;
         // accumulate launches read D in D's own layout (sub2, when the caller's C is laid out differently or conjugated)
-        const cutensorStatus_t st = cutensorContract(handle, (!first && plan.sub2) ? plan.sub2.get() : plan.sub1.get(), alpha, static_cast<const char*>(A) + oA * es,
-                                                     static_cast<const char*>(B) + oB * es, first ? beta : one, c, d, workspace, workspaceSize, stream);
+        const cutensorStatus_t st = cutensorContract(handle, (!first && plan.sub2) ? plan.sub2.get() : plan.sub1.get(), alpha, static_cast<const char*>(A) + oA * esA,
+                                                     static_cast<const char*>(B) + oB * esB, first ? beta : one, c, d, workspace, workspaceSize, stream);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
         size_t i = 0;
         for (; i < n; ++i) {
@@ -1988,6 +2001,8 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
             n += std::snprintf(buf + n, len - n, ",\"nt\":%d", tab[k].nt);
         if (n > 0 && (size_t)n < len && plan->choice.family == 2 && k >= 0)
             n += std::snprintf(buf + n, len - n, ",\"orientA\":%d,\"orientB\":%d,\"vec\":%d,\"elem\":%d", tab[k].layA, tab[k].layB, tab[k].vec, tab[k].elem);
+        // a mixed fp64 x complex128 plan: which of the CALLER's inputs is the real one (0 = A, 1 = B); "vec" above is that operand's width
+        if (n > 0 && (size_t)n < len && plan->view.realSide >= 0) n += std::snprintf(buf + n, len - n, ",\"real\":%d", plan->view.real_input());
         // 16-bit family: whether the launch is the RAG instantiation (masked / repaired last K-tile), and the strip plan — interior
         // [0, mInt) x [0, nInt) on `kernel`, the two edge strips as one launch of the 64 x 64 tile (ContractionChoice::stripKernel)
         if (n > 0 && (size_t)n < len && plan->choice.family == 1 && k >= 0)

@@ -282,7 +282,10 @@ cutensorStatus_t cutensorCreateBlockSparseContraction(const cutensorHandle_t han
     if (desc == nullptr || descA == nullptr || descB == nullptr || descC == nullptr || descD == nullptr || descCompute == nullptr)
         return CUTENSOR_STATUS_INVALID_VALUE;
     if (opA != CUTENSOR_OP_IDENTITY || opB != CUTENSOR_OP_IDENTITY || opC != CUTENSOR_OP_IDENTITY) return CUTENSOR_STATUS_NOT_SUPPORTED;
-    if (descA->dtype != descB->dtype || descA->dtype != descC->dtype || descA->dtype != descD->dtype) return CUTENSOR_STATUS_NOT_SUPPORTED;
+    if (descA->dtype != descB->dtype || descA->dtype != descC->dtype || descA->dtype != descD->dtype) {
+        CT_LOG("block-sparse contraction: mixed data types (the R_64F x C_64F rows belong to the dense pairwise contraction alone)");
+        return CUTENSOR_STATUS_NOT_SUPPORTED;
+    }
     // C is read through D's block descriptors and untouched output blocks are cleared as packed blocks: C must be laid out
     // exactly like D (the sample passes one descriptor for both, blocksparse.cu:177-182) and D's blocks must be packed
     if (descC->sections != descD->sections || descC->strides != descD->strides || descC->coords != descD->coords || !descD->strides.empty())

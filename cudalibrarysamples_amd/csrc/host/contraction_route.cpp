@@ -112,7 +112,8 @@ bool split_lone_modes(const cutensorOperationDescriptor& desc, TwoStepSplit& out
         red.D = red.C;
         red.opReduce = CUTENSOR_OP_ADD;
         red.compute = desc.compute;
-        red.scalarType = desc.scalarType;
+        // (the real input of a mixed fp64 x complex128 contraction is summed as what it is: a real fp64 reduction, double scalars)
+        red.scalarType = (X.desc.dtype == HIP_R_64F && desc.scalarType == HIP_C_64F) ? HIP_R_64F : desc.scalarType;
         return true;
     };
     TensorUse keptA, keptB;
@@ -396,8 +397,8 @@ static bool plan_repack(const cutensorHandle* handle, const cutensorOperationDes
 
 // pointer alignment the offset operands of a peeled contraction still have
 static void peel_fix_alignment(cutensorOperationDescriptor& inner, const std::vector<PeelMode>& peel) {
-    const int64_t es = (int64_t)dtype_size(inner.A.desc.dtype);
     auto fix = [&](TensorUse& t, int which) {
+        const int64_t es = (int64_t)dtype_size(t.desc.dtype);      // each tensor's own (a mixed contraction's real input: 8 bytes)
         uint32_t a = t.desc.alignment;
         for (const PeelMode& pm : peel) {
             const int64_t s = which == 0 ? pm.sA : which == 1 ? pm.sB : which == 2 ? pm.sC : pm.sD;

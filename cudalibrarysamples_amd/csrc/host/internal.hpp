@@ -103,6 +103,13 @@ struct ContractionView {
                                          // (gett_f32.hip) need; the LDS-DMA ring kernels take layA / layB as they are (round 6)
     uint32_t alignA = 0, alignB = 0;     // descriptor alignment (bytes) of kernel-A / kernel-B
     uint32_t alignD = 0;                 // ... of the output
+    // The mixed rows of the type table (one input real fp64, the other one, C and D complex128): which KERNEL operand is the real one —
+    // 0 kernel-A, 1 kernel-B; -1: both inputs have `dtype`.  `dtype` stays the output's type; byte sizes, alignment and vector widths
+    // of an input come from type_of().
+    int      realSide = -1;
+    hipDataType type_of(bool slotA) const { return realSide == (slotA ? 0 : 1) ? HIP_R_64F : dtype; }
+    // ... and which of the CALLER's inputs that is (0 = A, 1 = B; -1 none)
+    int real_input() const { return realSide < 0 ? -1 : (realSide ^ (swapped ? 1 : 0)); }
 };
 
 // The shape of a contraction plan: what cutensorCreatePlan built and cutensorContract runs (cutensorPlan::planKind)
@@ -260,6 +267,7 @@ struct cutensorPlan {
     int         triOrder[3] = {0, 1, 2};
     OpKind      kind;
     hipDataType dtype = HIP_R_32F;
+    hipDataType dtypeA = HIP_R_32F, dtypeB = HIP_R_32F;   // contractions: the caller's A and B (they differ from `dtype` in a mixed fp64 x complex128 plan)
     hipDataType scalarType = HIP_R_32F;
     uint64_t    requiredWorkspace = 0;
     uint32_t    alignA = 0, alignB = 0, alignC = 0, alignD = 0;  // pointer alignment the plan relies on
@@ -306,7 +314,8 @@ struct PlanMemoKey {
     uint8_t  op[4] = {0, 0, 0, 0};                 // opA, opB, opC, opReduce
     uint8_t  present = 0, operandsStreamed = 0, dtypeD = 0, dtypeC = 0;   // (dtype above is A's; C's is 255 when there is no C)
     uint32_t used = 0;                             // int64 words of data[] in use
-    uint32_t pad2_ = 0;                            // (no implicit padding anywhere in the head: it is hashed and compared bytewise)
+    uint32_t dtypeB = 0;                           // B's type + 1 where it differs from A's (mixed contractions), else 0
+                                                   // (no implicit padding anywhere in the head: it is hashed and compared bytewise)
     int64_t  data[3 * kMaxModes];                  // per tensor: modes, extents, strides
     uint64_t hash() const;
     bool operator==(const PlanMemoKey& o) const;

@@ -102,14 +102,26 @@ cutensorStatus_t build_contraction_view(const cutensorOperationDescriptor& op, C
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "repeated mode label inside one tensor");
     if (C.modes != D.modes) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "modes of C and D differ");
     if (C.desc.extent != D.desc.extent) return fail(CUTENSOR_STATUS_INVALID_VALUE, "extents of C and D differ");
-    if (A.desc.dtype != B.desc.dtype || A.desc.dtype != C.desc.dtype || C.desc.dtype != D.desc.dtype)
+    // one data type for all four tensors — or one of the two mixed rows of the type table: a real fp64 input, the other input, C and D
+    // complex128, complex double scalars, COMPUTE_DESC_64F
+    const bool mixedIn = A.desc.dtype != B.desc.dtype;
+    if (C.desc.dtype != D.desc.dtype || (!mixedIn && A.desc.dtype != C.desc.dtype))
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types");
+    if (mixedIn) {
+        const bool rowA = A.desc.dtype == HIP_R_64F && B.desc.dtype == HIP_C_64F, rowB = A.desc.dtype == HIP_C_64F && B.desc.dtype == HIP_R_64F;
+        if (!(rowA || rowB) || D.desc.dtype != HIP_C_64F)
+            return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: only R_64F x C_64F (either order) into C_64F C and D");
+        if (op.kind != OpKind::Contraction) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: pairwise contractions only");
+        if (op.scalarType != HIP_C_64F) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: the scalars are complex double");
+        if (op.compute == nullptr || op.compute->id != 5)
+            return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mixed data types: R_64F x C_64F contracts under COMPUTE_DESC_64F only");
+    }
     if (A.op != CUTENSOR_OP_IDENTITY && A.op != CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "opA");
     if (B.op != CUTENSOR_OP_IDENTITY && B.op != CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "opB");
     if (C.op != CUTENSOR_OP_IDENTITY && C.op != CUTENSOR_OP_CONJ) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "opC");
 
     v = ContractionView{};
-    v.dtype = A.desc.dtype;
+    v.dtype = D.desc.dtype;      // (== A's, but in a mixed contraction)
 
     // gather distinct labels in a stable order: A's, then B's, then C's
     std::vector<int32_t> labels;
@@ -162,6 +174,7 @@ cutensorStatus_t build_contraction_view(const cutensorOperationDescriptor& op, C
     }
     v.K = gK;
     v.L = gL;
+    if (mixedIn) v.realSide = ((A.desc.dtype == HIP_R_64F) != v.swapped) ? 0 : 1;
 
     auto bySA = [](const CanonMode& x, const CanonMode& y) { return x.sA < y.sA; };
     auto bySB = [](const CanonMode& x, const CanonMode& y) { return x.sB < y.sB; };
@@ -767,6 +780,10 @@ static constexpr double kF64xEffReal = 0.66, kF64xEffCplx = 0.67;
 // ... and what the fp64 kernels of this family sustain of THEIR MFMA rate where they stage 16-byte units: 60-63 of 78.6 TFLOP/s at fp64
 // 4096^3, 62 at complex128 2048^3
 static constexpr double kF64GenEff = 0.78;
+// ... and the mixed fp64 x complex128 kernels (gett_gen_rc64.inc; 4 real flops per multiply-add: half of complex128's MFMAs): measured,
+// 58.0 / 58.85 TFLOP/s = 0.738 / 0.749 of 78.6 at 2048^3 'mk,kn' with the real tensor as A / as B, median of five alternated rounds
+// (profiles/rc64_compute.jsonl, the two {"record": "summary"} lines, "efficiency_over_78.6"); 57.9-59.1 on the other 2048^3 layouts
+static constexpr double kRc64GenEff = 0.74;
 // complex64 data: what gett_gen_kernel<GEN_C32> sustains of the 157.3 TFLOP/s of v_mfma_f32_16x16x4_f32 where it stages 16-byte units, and
 // what the reduced-precision complex64 kernels (gett_gen_c32x.inc) sustain of the 16-bit MFMA rate (2516.6 TFLOP/s; a third of it for the
 // three products of TF32), on 8 real flops per complex multiply-add: fitted to the 32F and the forced-path rows of the 2048^3 and 4096^3
@@ -792,7 +809,7 @@ static int gen_operand_vec(const ContractionView& v, bool slotA, int orient, int
     if (lead.empty()) return 1;
     const CanonMode& m0 = lead.front();
     if ((slotA ? m0.sA : m0.sB) != 1) return 1;
-    const int64_t es = (int64_t)dtype_size(v.dtype);
+    const int64_t es = (int64_t)dtype_size(v.type_of(slotA));
     const uint32_t align = slotA ? v.alignA : v.alignB;
     for (int V = maxV; V > 1; V >>= 1) {
         if (m0.extent % V != 0 || align % (uint32_t)(V * es) != 0) continue;
@@ -813,14 +830,19 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     const int elem = (v.dtype == HIP_R_32F) ? (gen_elem_is_f32x(f32xElem) ? f32xElem : -1)
                    : (v.dtype == HIP_R_64F && f32xElem == GEN_F64_F32) || (v.dtype == HIP_C_64F && f32xElem == GEN_C64_C32) ? f32xElem
                    : (v.dtype == HIP_C_32F && gen_elem_is_c32x(f32xElem)) ? f32xElem      // complex64 data under 16BF / 16F / TF32 (gett_gen_c32x.inc)
+                   : (v.realSide >= 0) ? (int)GEN_RC64                                    // one real fp64 input into complex128 (gett_gen_rc64.inc)
                    : gen_elem_of(v.dtype);
     if (elem < 0 || v.wide) return false;
     const bool f32x = gen_elem_is_f32x(elem), f64x = gen_elem_is_f64x(elem), c32x = gen_elem_is_c32x(elem);
     const int maxV = (elem == GEN_C64 || elem == GEN_C64_C32) ? 1 : (elem == GEN_F64 || elem == GEN_C32 || elem == GEN_F64_F32 || c32x) ? 2 : f32x ? 4 : 8;
+    // GEN_RC64: one width per operand — the real one 16-byte lanes (2) or 8-byte gathers, the complex one always single elements — and
+    // the table row names the real operand's (GettKernelInfo::vec) and its side (::variant)
+    const bool rc = elem == GEN_RC64;
     int orient[2], vec[2];
     for (int o = 0; o < 2; ++o) {
         const bool slotA = o == 0;
-        const int vK = gen_operand_vec(v, slotA, 1, maxV), vF = gen_operand_vec(v, slotA, 0, maxV);
+        const int maxVo = rc ? (o == v.realSide ? 2 : 1) : maxV;
+        const int vK = gen_operand_vec(v, slotA, 1, maxVo), vF = gen_operand_vec(v, slotA, 0, maxVo);
         if (vK > 1 && vK >= vF) { orient[o] = 1; vec[o] = vK; }
         else if (vF > 1)        { orient[o] = 0; vec[o] = vF; }
         else {
@@ -832,7 +854,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
             vec[o] = 1;
         }
     }
-    int V = std::min(vec[0], vec[1]);
+    int V = rc ? vec[v.realSide] : std::min(vec[0], vec[1]);
     if (elem <= GEN_F16 && V == 4) V = 2;          // instantiated widths: 8 / 2 / 1 (16-bit), 2 / 1 (fp64, complex64), 1 (complex128)
     if (f32x && V == 2) V = 1;                     // 4 / 1 (fp32 data, reduced-precision compute)
     int count = 0;
@@ -840,7 +862,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     // candidates of this (type, V, orientation pair): the table lists the larger tile first
     int big = -1, small = -1;
     for (int i = 0; i < count; ++i)
-        if (tab[i].elem == elem && tab[i].vec == V && tab[i].layA == orient[0] && tab[i].layB == orient[1]) {
+        if (tab[i].elem == elem && tab[i].vec == V && tab[i].layA == orient[0] && tab[i].layB == orient[1] && (!rc || tab[i].variant == v.realSide)) {
             if (big < 0) big = i;
             small = i;
         }
@@ -878,7 +900,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
     // rough time: the family's MFMA rate for the type at ~50 % utilisation (only used for logs / describe)
     const double flopPerClkCU = (elem <= GEN_F16) ? 4096.0 : (elem == GEN_C32 || f64x) ? 256.0 : f32x ? (elem == GEN_F32_BF16X3 ? 4096.0 / 3.0 : 4096.0)
                               : c32x ? (elem == GEN_C32_BF16X3 ? 4096.0 / 3.0 : 4096.0) : 128.0;
-    const double flops = ((elem == GEN_C32 || elem == GEN_C64 || elem == GEN_C64_C32 || c32x) ? 8.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
+    const double flops = ((elem == GEN_C32 || elem == GEN_C64 || elem == GEN_C64_C32 || c32x) ? 8.0 : rc ? 4.0 : 2.0) * k.bm * k.bn * (double)c.kPerSlice;
     c.estimateUs = std::ceil(tiles * c.splitK / (double)numCUs) * flops / (flopPerClkCU * 2.4e9 * 0.5) * 1e6 + 2.0;
     if (f32x) {
         // The estimate that decides between these kernels and the ranked fp32 candidates (cutensorCreatePlan).  Waves of workgroups at
@@ -891,7 +913,7 @@ bool pick_gen_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         const double bytes = 4.0 * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
         c.estimateUs = std::max(tCompute, bytes / 4.0e12 * 1e6) + 4.0;
     }
-    if (f64x) c.estimateUs = gen_f64_measured_estimate_us(v, c, numCUs);
+    if (f64x || rc) c.estimateUs = gen_f64_measured_estimate_us(v, c, numCUs);
     if (c32x) c.estimateUs = gen_c32_measured_estimate_us(v, c, numCUs);
     return true;
 }
@@ -908,13 +930,15 @@ double gen_f64_measured_estimate_us(const ContractionView& v, const ContractionC
     if (c.family != 2 || c.kernel < 0 || c.kernel >= count) return -1.0;
     const GettKernelInfo& k = tab[c.kernel];
     const bool f64x = gen_elem_is_f64x(k.elem);
-    if (!f64x && k.elem != GEN_F64 && k.elem != GEN_C64) return -1.0;
+    const bool rc = k.elem == GEN_RC64;      // complex128's formula at half the MFMA work (4 real flops per multiply-add); the real operand moves 8-byte elements
+    if (!f64x && !rc && k.elem != GEN_F64 && k.elem != GEN_C64) return -1.0;
     const bool cplx = k.elem == GEN_C64 || k.elem == GEN_C64_C32;
-    const double rate = (f64x ? 256.0 : 128.0) * 2.4e9 * (!f64x ? kF64GenEff : cplx ? kF64xEffCplx : kF64xEffReal);      // flop / s / CU
+    const double rate = (f64x ? 256.0 : 128.0) * 2.4e9 * (rc ? kRc64GenEff : !f64x ? kF64GenEff : cplx ? kF64xEffCplx : kF64xEffReal);      // flop / s / CU
     const double tiles = std::ceil((double)v.totM / k.bm) * std::ceil((double)v.totN / k.bn) * (double)v.totL;
-    const double flops = (cplx ? 8.0 : 2.0) * k.bm * k.bn * (double)(c.kPerSlice ? c.kPerSlice : v.totK);
+    const double flops = (cplx ? 8.0 : rc ? 4.0 : 2.0) * k.bm * k.bn * (double)(c.kPerSlice ? c.kPerSlice : v.totK);
     const double tCompute = std::ceil(tiles * std::max<uint32_t>(c.splitK, 1u) / (double)numCUs) * flops / rate * 1e6;
-    const double bytes = (double)dtype_size(v.dtype) * (double)v.totL * ((double)v.totM * v.totK + (double)v.totN * v.totK + (double)v.totM * v.totN);
+    const double bytes = (double)v.totL * ((double)dtype_size(v.type_of(true)) * (double)v.totM * v.totK + (double)dtype_size(v.type_of(false)) * (double)v.totN * v.totK +
+                                           (double)dtype_size(v.dtype) * (double)v.totM * v.totN);
     return std::max(tCompute, bytes / 4.0e12 * 1e6) + 2.0;
 }
 
@@ -983,14 +1007,14 @@ void fill_gett_params(const ContractionView& v, const ContractionChoice& c, Gett
     p.nBlocks = (uint32_t)((uint64_t)p.tilesM * p.tilesN * p.splitK * v.totL);
 
     {   // bytes from an operand's first element to one past its last (cutensorContract adds the pointer: GettParams::endA / endB)
-        const uint64_t es = (uint64_t)dtype_size(v.dtype);
+        const uint64_t esA = (uint64_t)dtype_size(v.type_of(true)), esB = (uint64_t)dtype_size(v.type_of(false));
         uint64_t spanA = 1, spanB = 1;
         for (const std::vector<CanonMode>* g : {&v.L, &v.M, &v.K})
             for (const CanonMode& m : *g) spanA += (uint64_t)(m.extent - 1) * (uint64_t)std::llabs(m.sA);
         for (const std::vector<CanonMode>* g : {&v.L, &v.N, &v.K})
             for (const CanonMode& m : *g) spanB += (uint64_t)(m.extent - 1) * (uint64_t)std::llabs(m.sB);
-        p.endA = spanA * es;
-        p.endB = spanB * es;
+        p.endA = spanA * esA;
+        p.endB = spanB * esB;
         p.ragged = (c.family == 1 && h16_needs_rag(v)) ? 1u : 0u;
         if (c.family == 1 && h16_sweep_ragged(v)) p.ragged |= 2u | ((uint32_t)h16_k_tiles(v) << 2);   // sweep-ragged K: the padded K-tile count
         if (c.family == 0 && v.dtype == HIP_R_32F && c.kernel >= 0) {

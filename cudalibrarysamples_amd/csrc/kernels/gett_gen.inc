@@ -53,10 +53,11 @@ struct GenCfg {
 // ---------------------------------------------------------------------------------------------
 // One operand of the K-tile: global -> registers -> LDS.
 // ---------------------------------------------------------------------------------------------
-template <int ES, int ORIENT, int ROWS, int BK, int V>
+// (ImgT: the LDS image — GenImage of the element size and K-tile, but for gett_gen_rc64.inc's real operand)
+template <int ES, int ORIENT, int ROWS, int BK, int V, class ImgT = GenImage<ES, BK>>
 struct GenOperand {
     using Map = GenUnitMap<ORIENT, ROWS, BK, V, 256>;
-    using Img = GenImage<ES, BK>;
+    using Img = ImgT;
     static constexpr int NU = Map::NU;
     static constexpr int UB = V * ES;                  // bytes per unit = per global load: 2, 4, 8 or 16
     static constexpr int DW = UB >= 4 ? UB / 4 : 1;    // staging dwords per unit

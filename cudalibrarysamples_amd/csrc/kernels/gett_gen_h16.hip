@@ -24,7 +24,8 @@ const GettKernelInfo* gett_gen_h16_kernels(int* count) {
 const GettKernelInfo* gett_gen_kernels(int* count) {
     static const std::vector<GettKernelInfo> merged = [] {
         std::vector<GettKernelInfo> v;
-        for (auto fn : {&gett_gen_h16_kernels, &gett_gen_f64_kernels, &gett_gen_cplx_kernels, &gett_gen_f32x_kernels, &gett_gen_f64x_kernels, &gett_gen_c32x_kernels}) {
+        for (auto fn : {&gett_gen_h16_kernels, &gett_gen_f64_kernels, &gett_gen_cplx_kernels, &gett_gen_f32x_kernels, &gett_gen_f64x_kernels, &gett_gen_c32x_kernels,
+                        &gett_gen_rc64_kernels}) {
             int n = 0;
             const GettKernelInfo* t = fn(&n);
             v.insert(v.end(), t, t + n);

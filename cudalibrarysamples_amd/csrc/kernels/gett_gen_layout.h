@@ -80,6 +80,35 @@ struct GenFrag {
     static CTAMD_HD int k_of(int s, int q, int h, int e) { return unit(s, q, h) * EPU + e; }
 };
 
+// The REAL fp64 operand of a mixed fp64 x complex128 product (gett_gen_rc64.inc): 8-byte elements at K-tile 8 = rows of 64 bytes
+// (GenImageR64), and ONE 16-byte unit per lane — logical unit 4 s + q of row r = the elements k = 2 q + j, j < 2, of k-block s.
+// That is GenFrag<16>'s (q, j) -> k assignment (complex128: two units of one element each, k = 2 q + h), which the complex operand
+// of the product uses: step j of the k-block multiplies real element j with the parts of complex element h = j.  GenFrag<8> (two units,
+// four elements k = 4 q + j, 16 k per block) is the all-fp64 kernels' map and does not pair with it.
+// Its LDS image: GenImage's arithmetic on 64-byte rows of 8-byte elements, with a swizzle of its own — unit ^ ((row >> 1) & 3).  Found
+// by tools/lds_swizzle_search.py ("rc64") among the GF(2)-linear maps of the row's low four bits: the fragment read (ds_read_b128, lane
+// (r, q) reads unit q of row r) is conflict-free, as under GenImage's 64-byte-row swizzle; the transposing 8-byte staging writes of a
+// free-contiguous operand (16 lanes = 16 or 32 consecutive rows at one k) are 2-way (V = 1) / 4-way (V = 2) where that one leaves them
+// 4- / 8-way — four units per row cannot spread them further; K-contiguous staging writes are conflict-free under both.
+struct GenImageR64 {
+    static constexpr int ES = 8, BK = 8;
+    static constexpr int RB = BK * ES;        // 64 bytes per row
+    static constexpr int UR = RB / 16;        // 4 units per row
+    static CTAMD_HD int sw(int row) { return (row >> 1) & 3; }
+    static CTAMD_HD int addr(int row, int k) {
+        const int kb = k * ES;
+        return row * RB + ((((kb >> 4) ^ sw(row)) & (UR - 1)) << 4) + (kb & 15);
+    }
+    static CTAMD_HD int unit_addr(int rb, int r, int unit) { return (rb + r) * RB + (((unit ^ sw(r)) & (UR - 1)) << 4); }
+};
+struct GenFragR64 {
+    static constexpr int UPL = 1;
+    static constexpr int EPU = 2;                       // doubles per 16-byte unit
+    static constexpr int KPB = 4 * UPL * EPU;           // 8 k per k-block, as GenFrag<16>
+    static CTAMD_HD int unit(int s, int q, int h) { return (4 * s + q) * UPL + h; }
+    static CTAMD_HD int k_of(int s, int q, int h, int e) { return unit(s, q, h) * EPU + e; }
+};
+
 // Row of accumulator register t of lane-group q inside a 16 x 16 fragment (column = lane & 15):
 // fp32 accumulators (v_mfma_f32_16x16x*): 4 q + t;  fp64 (v_mfma_f64_16x16x4_f64): q + 4 t.
 template <bool ACC64>

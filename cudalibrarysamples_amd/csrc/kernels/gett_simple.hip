@@ -134,7 +134,9 @@ __global__ void __launch_bounds__(256) gett_wide_kernel(const WideParams p) {
 
 // Complex data: D = alpha * op(A) * op(B) + beta * op(C) with op = identity or conjugate
 // (cuTENSOR/contraction_jit.cu:31-41: std::complex<float> tensors and scalars).  R = float or double.
-template <typename R>
+// REAL (WideParams::realOperand; complex128 C / D only): 1 — kernel-A holds real values of type R, 2 — kernel-B does; that input is read
+// as what it is (its strides count reals, its conjugation is the identity), no complex copy of it is made.  0: both inputs complex.
+template <typename R, int REAL = 0>
 __global__ void __launch_bounds__(256) gett_wide_complex_kernel(const WideParams p) {
     struct Cx { R re, im; };
     const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -150,6 +152,8 @@ __global__ void __launch_bounds__(256) gett_wide_complex_kernel(const WideParams
     }
     const Cx* A = static_cast<const Cx*>(p.A) + oA;
     const Cx* B = static_cast<const Cx*>(p.B) + oB;
+    const R* Ar = static_cast<const R*>(p.A) + oA;      // (REAL: the real input's elements)
+    const R* Br = static_cast<const R*>(p.B) + oB;
     const R sa = p.conjA ? (R)-1 : (R)1, sb = p.conjB ? (R)-1 : (R)1;
     R accRe = 0, accIm = 0;
     for (uint32_t k = 0; k < p.kTotal; ++k) {
@@ -162,10 +166,22 @@ __global__ void __launch_bounds__(256) gett_wide_complex_kernel(const WideParams
             ka += digit * m.sA; kb += digit * m.sB;
             r = q;
         }
-        const Cx a = A[ka], b = B[kb];
-        const R aim = sa * a.im, bim = sb * b.im;
-        accRe += a.re * b.re - aim * bim;
-        accIm += a.re * bim + aim * b.re;
+        if constexpr (REAL == 1) {
+            const R a = Ar[ka];
+            const Cx b = B[kb];
+            accRe += a * b.re;
+            accIm += a * (sb * b.im);
+        } else if constexpr (REAL == 2) {
+            const Cx a = A[ka];
+            const R b = Br[kb];
+            accRe += a.re * b;
+            accIm += (sa * a.im) * b;
+        } else {
+            const Cx a = A[ka], b = B[kb];
+            const R aim = sa * a.im, bim = sb * b.im;
+            accRe += a.re * b.re - aim * bim;
+            accIm += a.re * bim + aim * b.re;
+        }
     }
     const R alRe = (R)p.alpha64, alIm = (R)p.alphaIm, beRe = (R)p.beta64, beIm = (R)p.betaIm;
     Cx out;
@@ -198,7 +214,9 @@ hipError_t launch_gett_wide(const WideParams& p, int dtype, bool accumulate64, h
             hipLaunchKernelGGL(gett_wide_complex_kernel<float>, dim3((unsigned)((p.outTotal + 255) / 256)), dim3(256), 0, stream, p);
             break;
         case HIP_C_64F:
-            hipLaunchKernelGGL(gett_wide_complex_kernel<double>, dim3((unsigned)((p.outTotal + 255) / 256)), dim3(256), 0, stream, p);
+            if (p.realOperand == 1) hipLaunchKernelGGL((gett_wide_complex_kernel<double, 1>), dim3((unsigned)((p.outTotal + 255) / 256)), dim3(256), 0, stream, p);
+            else if (p.realOperand == 2) hipLaunchKernelGGL((gett_wide_complex_kernel<double, 2>), dim3((unsigned)((p.outTotal + 255) / 256)), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL(gett_wide_complex_kernel<double>, dim3((unsigned)((p.outTotal + 255) / 256)), dim3(256), 0, stream, p);
             break;
         default: return hipErrorInvalidValue;
     }

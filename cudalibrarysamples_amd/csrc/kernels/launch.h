@@ -45,9 +45,11 @@ struct GettKernelInfo {
     int nt;              // 1: operands are streamed with the nontemporal policy (no Infinity-Cache allocation): ranked only for
                          //    problems that read every operand byte once and whose operands exceed the Infinity Cache anyway
     int elem;            // general family (gett_gen_kernels): GenElem of the instantiation
-    int vec;             // general family: elements per staged unit = per global load (both operands)
+    int vec;             // general family: elements per staged unit = per global load (both operands; GEN_RC64: the real operand's — the
+                         // complex one always loads single 16-byte elements)
     const char* name;    // the __global__ template the entry launches (ctamdDescribePlan's "kname")
-    int variant;         // aligned 16-bit family: H16Variant of the entry (0 in the other families' tables)
+    int variant;         // aligned 16-bit family: H16Variant of the entry (0 in the other families' tables, but for the GEN_RC64 rows of the
+                         // general family: which kernel operand is the real one — 0 kernel-A, 1 kernel-B)
 };
 
 // element types of the general MFMA family (gett_gen.inc)
@@ -61,7 +63,10 @@ enum GenElem : int { GEN_BF16 = 0, GEN_F16 = 1, GEN_F64 = 2, GEN_C32 = 3, GEN_C6
                      // complex64 DATA under a reduced-precision compute descriptor (gett_gen_c32x.inc): real and imaginary parts rounded to
                      // bf16 / fp16, or split into two bf16 planes each (COMPUTE_DESC_TF32), on their way into LDS; four (twelve) 16-bit MFMAs per
                      // complex product; fp32 accumulators, float2 partials and the complex64 epilogue and fold of GEN_C32
-                     GEN_C32_BF16 = 10, GEN_C32_F16 = 11, GEN_C32_BF16X3 = 12 };
+                     GEN_C32_BF16 = 10, GEN_C32_F16 = 11, GEN_C32_BF16X3 = 12,
+                     // one real fp64 operand, the other one and C / D complex128 (gett_gen_rc64.inc): two fp64 MFMAs per product into two
+                     // accumulators (re, im), double2 partials and the complex128 epilogue and fold of GEN_C64
+                     GEN_RC64 = kGenElemRC64 };
 inline bool gen_elem_is_f32x(int elem) { return elem >= GEN_F32_BF16 && elem <= GEN_F32_BF16X3; }
 inline bool gen_elem_is_f64x(int elem) { return elem == GEN_F64_F32 || elem == GEN_C64_C32; }
 inline bool gen_elem_is_c32x(int elem) { return elem >= GEN_C32_BF16 && elem <= GEN_C32_BF16X3; }
@@ -70,7 +75,7 @@ inline bool gen_elem_is_c32x(int elem) { return elem >= GEN_C32_BF16 && elem <= 
 inline bool gen_elem_f32_partials(int elem) { return elem == GEN_BF16 || elem == GEN_F16 || gen_elem_is_f32x(elem); }
 // bytes of one split-K partial element
 inline unsigned gen_elem_partial_bytes(int elem) {
-    return (gen_elem_f32_partials(elem) || elem == GEN_F64_F32) ? 4u : (elem == GEN_C64) ? 16u : 8u;
+    return (gen_elem_f32_partials(elem) || elem == GEN_F64_F32) ? 4u : (elem == GEN_C64 || elem == GEN_RC64) ? 16u : 8u;
 }
 
 // fp32 data, fp32 MFMA (v_mfma_f32_16x16x4_f32)
@@ -90,7 +95,7 @@ const GettKernelInfo* gett_h16p_kernels(int* count);   // gett_h16p.hip (persist
 // complex64 / complex128 — register-staged, any strides and extents (gett_gen.inc; the table is the concatenation of the three
 // translation units gett_gen_h16.hip / gett_gen_f64.hip / gett_gen_cplx.hip, then — appended, so that every earlier index stays — the
 // reduced-precision fp32 kernels of gett_gen_f32x.hip, then the single-precision-compute fp64 / complex128 kernels of gett_gen_f64x.hip,
-// then the reduced-precision complex64 kernels of gett_gen_c32x.hip)
+// then the reduced-precision complex64 kernels of gett_gen_c32x.hip, then the mixed fp64 x complex128 kernels of gett_gen_rc64.hip)
 const GettKernelInfo* gett_gen_kernels(int* count);
 const GettKernelInfo* gett_gen_h16_kernels(int* count);
 const GettKernelInfo* gett_gen_f64_kernels(int* count);
@@ -98,9 +103,10 @@ const GettKernelInfo* gett_gen_cplx_kernels(int* count);
 const GettKernelInfo* gett_gen_f32x_kernels(int* count);
 const GettKernelInfo* gett_gen_f64x_kernels(int* count);
 const GettKernelInfo* gett_gen_c32x_kernels(int* count);
+const GettKernelInfo* gett_gen_rc64_kernels(int* count);
 // split-K fold of the general family's fp64 / complex kernels: D = alpha * sum_s partial[s] + beta * op(C); partials
 // [slice][L][M][N] in the accumulator type of `elem` (GEN_F64: double, GEN_C32 and GEN_C32_BF16 / _F16 / _BF16X3: float2, GEN_C64: double2; GEN_F64_F32: float and
-// GEN_C64_C32: float2, summed and scaled in fp64 on fp64 C / D — gett_gen_f64x.hip)
+// GEN_C64_C32: float2, summed and scaled in fp64 on fp64 C / D — gett_gen_f64x.hip; GEN_RC64: double2, folded as GEN_C64)
 hipError_t launch_gen_splitk_reduce(const SplitKReduceParams& p, int elem, hipStream_t stream);
 hipError_t launch_gen_f64x_splitk_reduce(const SplitKReduceParams& p, int elem, hipStream_t stream);
 

@@ -12,6 +12,10 @@ namespace ctamd {
 
 constexpr int kMaxGroupModes = 4;   // modes per group after fusion (more => NOT_SUPPORTED)
 
+// GenElem code (launch.h) of the mixed kernels of the general MFMA family (gett_gen_rc64.inc): one operand real fp64, the other one, C and D
+// complex128 — the next free code after GEN_C32_BF16X3
+constexpr int kGenElemRC64 = 13;
+
 // Exact unsigned division n / d for n < 2^31, d in [2, 2^31): q = mulhi(n, magic) >> shift.
 struct FastDiv {
     uint32_t d;
@@ -150,6 +154,9 @@ struct WideParams {
     // complex data (HIP_C_32F / HIP_C_64F): imaginary parts of the scalars, conjugation of each input
     double      alphaIm, betaIm;
     int32_t     conjA, conjB, conjC;
+    // complex128 C / D with ONE real fp64 input (the mixed rows of the type table): 1 — kernel-A holds doubles, 2 — kernel-B does; its
+    // strides count doubles and its conjugation is the identity.  0: both inputs have the data type.  (Four bytes of what was tail padding.)
+    int32_t     realOperand;
 };
 
 // Second stage of split-K: D = alpha * sum_s partial[s] + beta * C

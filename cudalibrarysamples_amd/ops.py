@@ -155,8 +155,13 @@ def _typed_value(value, dtype):
 
 def contraction_plan(handle, extA, modesA, extB, modesB, extC, modesC, dtype=ct.R_32F, strideA=None,
                      strideB=None, strideC=None, strideD=None, compute=None, alignment=128, opA=ct.OP_IDENTITY,
-                     opB=ct.OP_IDENTITY, opC=ct.OP_IDENTITY, **plan_kw):
-    dA, dB, dC = _desc3(handle, [(extA, strideA), (extB, strideB), (extC, strideC)], dtype, alignment)
+                     opB=ct.OP_IDENTITY, opC=ct.OP_IDENTITY, dtypeA=None, dtypeB=None, **plan_kw):
+    """dtypeA / dtypeB: the data type of A / of B where it differs from that of C and D (dtype) — the mixed rows of the type table:
+    dtype=ct.C_64F with dtypeA=ct.R_64F or dtypeB=ct.R_64F (a real fp64 operand into a complex128 contraction, compute "64F", complex
+    scalars); None: the same type."""
+    dA = tensor_descriptor(handle, extA, strideA, dtype if dtypeA is None else dtypeA, alignment)
+    dB = tensor_descriptor(handle, extB, strideB, dtype if dtypeB is None else dtypeB, alignment)
+    dC = tensor_descriptor(handle, extC, strideC, dtype, alignment)
     dD = tensor_descriptor(handle, extC, strideD, dtype, alignment) if strideD is not None else dC
     op = ctypes.c_void_p()
     st = ct.cutensorCreateContraction(handle.h, ctypes.byref(op), dA, ct.i32(modesA), _unary(opA), dB, ct.i32(modesB),

@@ -39,10 +39,22 @@ def get_handle():
 class EinsumPlan:
     """Parsed + planned equation for fixed shapes/dtype (plan()/execute() split of python/einsum.h)."""
 
-    def __init__(self, equation, a_shape, b_shape, dtype, conj_a=False, conj_b=False, compute=None):
-        compute = _check_compute(compute, dtype)
-        self.e = ct.lib.ctamdEinsumCreate(equation.encode(), ct.i64(list(a_shape)), len(a_shape),
-                                          ct.i64(list(b_shape)), len(b_shape), _TORCH2CT[dtype])
+    def __init__(self, equation, a_shape, b_shape, dtype, conj_a=False, conj_b=False, compute=None, dtype_b=None):
+        """dtype_b: the second operand's type where it differs from the first one's — one float64 and one complex128 tensor, in either
+        order (the output is complex128, compute None or "64F"); None: the same type."""
+        if dtype_b is None or dtype_b == dtype:
+            compute = _check_compute(compute, dtype)
+            self.e = ct.lib.ctamdEinsumCreate(equation.encode(), ct.i64(list(a_shape)), len(a_shape),
+                                              ct.i64(list(b_shape)), len(b_shape), _TORCH2CT[dtype])
+        else:
+            if {dtype, dtype_b} != {torch.float64, torch.complex128}:
+                raise ValueError("cutensor einsum: operands of different types must be one float64 and one complex128 tensor, got %s and %s" % (dtype, dtype_b))
+            if compute not in (None, "64F"):
+                raise ValueError("cutensor einsum: float64 x complex128 contracts under compute None or '64F', got %r" % (compute,))
+            compute = None
+            self.e = ct.lib.ctamdEinsumCreateTyped(equation.encode(), ct.i64(list(a_shape)), len(a_shape), ct.i64(list(b_shape)), len(b_shape),
+                                                   _TORCH2CT[dtype], _TORCH2CT[dtype_b])
+            dtype = torch.complex128
         if not self.e or not ct.lib.ctamdEinsumIsInitialized(self.e):
             raise ValueError("cutensor einsum: '%s' not supported for shapes %s, %s" % (equation, tuple(a_shape), tuple(b_shape)))
         if conj_a or conj_b:
@@ -107,7 +119,16 @@ def einsum(equation, a, b=None, conj_a=False, conj_b=False, compute=None):
     operand inside the contraction (python/cutensor/torch/einsum.py:50-61 uses them for complex gradients).  compute: None (the
     data type's default), on float32 / complex64 tensors "TF32" / "16BF" / "16F", on float64 / complex128 tensors "32F", to permit
     reduced-precision products (see _COMPUTE)."""
-    compute = _check_compute(compute, a.dtype)
+    # one float64 and one complex128 tensor, in either order: the real operand is contracted as it is, into a complex128 output
+    mixed = b is not None and b.dtype != a.dtype
+    if mixed:
+        if {a.dtype, b.dtype} != {torch.float64, torch.complex128}:
+            raise ValueError("cutensor einsum: operands of different types must be one float64 and one complex128 tensor, got %s and %s" % (a.dtype, b.dtype))
+        if compute not in (None, "64F"):
+            raise ValueError("cutensor einsum: float64 x complex128 contracts under compute None or '64F', got %r" % (compute,))
+        compute = None
+    else:
+        compute = _check_compute(compute, a.dtype)
     if not a.is_cuda:
         raise RuntimeError("cutensor einsum runs on the GPU only (there is no CPU path)")
     a = a.contiguous()
@@ -115,10 +136,13 @@ def einsum(equation, a, b=None, conj_a=False, conj_b=False, compute=None):
     key = (equation, tuple(a.shape), tuple(b.shape) if b is not None else (), a.dtype, bool(conj_a), bool(conj_b))
     if compute is not None:
         key += (compute,)          # (the default keeps the key it always had)
+    if mixed:
+        key += (("dtype_b", b.dtype),)
     plan = _plans.get(key)
     if plan is None:
-        plan = _plans[key] = EinsumPlan(equation, a.shape, b.shape if b is not None else (), a.dtype, conj_a, conj_b, compute)
-    out = torch.empty(plan.output_shape, dtype=a.dtype, device=a.device)
+        plan = _plans[key] = EinsumPlan(equation, a.shape, b.shape if b is not None else (), a.dtype, conj_a, conj_b, compute,
+                                        b.dtype if mixed else None)
+    out = torch.empty(plan.output_shape, dtype=plan.dtype, device=a.device)
     try:
         ws = _get_workspace(a.device, plan.required_workspace)
     except torch.cuda.OutOfMemoryError:
@@ -191,6 +215,8 @@ class EinsumFunction(torch.autograd.Function):
             raise RuntimeError("The subscript indicates two inputs, but only one was passed")
         if not is_binary and input_1 is not None:
             raise RuntimeError("The subscript indicates one input, but two were passed")
+        if input_1 is not None and input_1.dtype != input_0.dtype:      # (einsum() itself takes float64 x complex128; its gradients are not built)
+            raise RuntimeError("EinsumFunction needs operands of one type, got %s and %s" % (input_0.dtype, input_1.dtype))
         out = einsum(equation, input_0.detach(), input_1.detach() if input_1 is not None else None)
         if is_binary:
             ctx.save_for_backward(input_0, input_1)

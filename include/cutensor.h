@@ -71,7 +71,13 @@ cutensorStatus_t cutensorCreateTensorDescriptor(const cutensorHandle_t      hand
 cutensorStatus_t cutensorDestroyTensorDescriptor(cutensorTensorDescriptor_t desc);
 
 /* ---- operation descriptors ------------------------------------------------------------------ */
-/* D = alpha * opA(A) * opB(B) + beta * opC(C)                          contraction.cu:162-168 */
+/* D = alpha * opA(A) * opB(B) + beta * opC(C)                          contraction.cu:162-168
+ * A, B, C and D share one data type — or form one of the two mixed rows of the type table:
+ *     A             B             C = D         compute                    scalars
+ *     CUTENSOR_R_64F CUTENSOR_C_64F CUTENSOR_C_64F CUTENSOR_COMPUTE_DESC_64F  complex double
+ *     CUTENSOR_C_64F CUTENSOR_R_64F CUTENSOR_C_64F CUTENSOR_COMPUTE_DESC_64F  complex double
+ * (the real tensor is contracted as it is: no complex copy, half the matrix work; CUTENSOR_OP_CONJ on it is the identity).
+ * Every other mixture, and every other compute descriptor on these two, is CUTENSOR_STATUS_NOT_SUPPORTED. */
 cutensorStatus_t cutensorCreateContraction(const cutensorHandle_t           handle,
                                            cutensorOperationDescriptor_t*   desc,
                                            const cutensorTensorDescriptor_t descA, const int32_t modeA[], cutensorOperator_t opA,
