@@ -2111,6 +2111,9 @@ int ctamdProfileEnd(cutensorHandle_t handle, float* meanMs, float* minMs) try {
 // 1 when this library reads the test / measurement switches (CTAMD_HOOK_ENV: the lib_hooks/ flavour)
 int ctamdTestHooksBuilt(void) try { return CTAMD_HOOKS_BUILT; } CTAMD_API_CATCH_INT
 
+// CUTENSOR_LOG_LEVEL as this library read it: libcutensorMg.so logs its refusals under the same switch without reading it itself
+int ctamdLogLevel(void) try { return log_level(); } CTAMD_API_CATCH_INT
+
 int ctamdKernelCount(void) try {
     int count = 0;
     (void)kernel_table(0, &count);

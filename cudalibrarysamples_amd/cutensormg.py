@@ -30,6 +30,13 @@ EXPORTS = {
     "cutensorMgCreateContractionPlan": (_vp, ctypes.POINTER(_vp), _vp, _vp, _i64p, ctypes.c_int64),
     "cutensorMgDestroyContractionPlan": (_vp,),
     "cutensorMgContraction": (_vp, _vp, _vp, _vpp, _vpp, _vp, _vpp, _vpp, _vpp, _vp, _vpp),
+    # the copy half of the API (include/cutensorMg.h: cuTENSORMg's public API, no sample calls it)
+    "cutensorMgCreateCopyDescriptor": (_vp, ctypes.POINTER(_vp), _vp, _i32p, _vp, _i32p),
+    "cutensorMgDestroyCopyDescriptor": (_vp,),
+    "cutensorMgCopyGetWorkspace": (_vp, _vp, _i64p, _i64p),
+    "cutensorMgCreateCopyPlan": (_vp, ctypes.POINTER(_vp), _vp, _i64p, ctypes.c_int64),
+    "cutensorMgDestroyCopyPlan": (_vp,),
+    "cutensorMgCopy": (_vp, _vp, _vpp, _vpp, _vpp, _vp, _vpp),
 }
 for _name, _args in EXPORTS.items():
     _f = getattr(lib, _name)
@@ -41,7 +48,10 @@ lib.ctamdMgDescribePlan.argtypes = [_vp, ctypes.c_char_p, ctypes.c_size_t]
 lib.ctamdMgDescribePlan.restype = ctypes.c_int
 lib.ctamdMgDescribeKBoxes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_char_p, ctypes.c_size_t]
 lib.ctamdMgDescribeKBoxes.restype = ctypes.c_int
-
+lib.ctamdMgDescribeCopyPlan.argtypes = [_vp, ctypes.c_char_p, ctypes.c_size_t]
+lib.ctamdMgDescribeCopyPlan.restype = ctypes.c_int
+lib.ctamdMgCopyReplayOnHost.argtypes = [_vp, _vpp, _vpp]
+lib.ctamdMgCopyReplayOnHost.restype = ctypes.c_int
 
 
 class HostView(ctypes.Structure):
@@ -169,6 +179,96 @@ class Contraction:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def describe_copy_plan(plan):
+    """ctamdMgDescribeCopyPlan -> dict: per handle device the launches (form, lane bytes, cells, grid), local / remote bytes, workspace;
+    the owner of every cell, the mode cap."""
+    import json
+    n = 1 << 16
+    while True:
+        buf = ctypes.create_string_buffer(n)
+        r = lib.ctamdMgDescribeCopyPlan(plan, buf, n)
+        if r >= 0:
+            return json.loads(buf.value.decode())
+        if r == -1:
+            raise ValueError("ctamdMgDescribeCopyPlan: invalid arguments")
+        n = -r + 16
+
+
+class CopyPlan:
+    """RAII bundle of the cuTENSORMg copy sequence for dst[dst.modes] = src[src.modes]: handle over `devices`, the two block-cyclic
+    descriptors, copy descriptor, workspace query and plan.  `dst` / `src` are dicts: modes (a string), extent, block and grid (one entry
+    per mode; default one block, one cell), optional elem_stride / block_stride (default packed) and owners (HIP device of every
+    cell; default the handle devices repeated cyclically)."""
+
+    def __init__(self, devices, dst, src, dtype=0, src_dtype=None):
+        self.devices = list(devices)
+        self.h = ctypes.c_void_p()
+        self.descs, self.cd, self.plan = [], ctypes.c_void_p(), ctypes.c_void_p()
+        check(cutensorMgCreate(ctypes.byref(self.h), len(self.devices), i32(self.devices)))
+        try:
+            self.layouts = []
+            for t, dt in ((dst, dtype), (src, dtype if src_dtype is None else src_dtype)):
+                ext = list(t["extent"])
+                bs = list(t.get("block") or ext)
+                dc = list(t.get("grid") or [1] * len(ext))
+                ncell = 1
+                for x in dc:
+                    ncell *= x
+                owners = list(t.get("owners") or [self.devices[i % len(self.devices)] for i in range(ncell)])
+                es_, bst = t.get("elem_stride"), t.get("block_stride")
+                d = ctypes.c_void_p()
+                check(cutensorMgCreateTensorDescriptor(self.h, ctypes.byref(d), len(ext), i64(ext), i64(es_) if es_ else None, i64(bs),
+                                                       i64(bst) if bst else None, i32(dc), ncell, i32(owners), dt))
+                self.descs.append(d)
+                self.layouts.append(dict(modes=t["modes"], ext=ext, bs=bs, dc=dc, owners=owners, ncell=ncell))
+            check(cutensorMgCreateCopyDescriptor(self.h, ctypes.byref(self.cd), self.descs[0], i32(list(dst["modes"])), self.descs[1],
+                                                 i32(list(src["modes"]))))
+            self.ws_sizes = (ctypes.c_int64 * len(self.devices))()
+            self.host_size = ctypes.c_int64(-1)
+            check(cutensorMgCopyGetWorkspace(self.h, self.cd, self.ws_sizes, ctypes.byref(self.host_size)))
+            check(cutensorMgCreateCopyPlan(self.h, ctypes.byref(self.plan), self.cd, self.ws_sizes, self.host_size.value))
+        except Exception:
+            self.close()
+            raise
+
+    def describe(self):
+        return describe_copy_plan(self.plan)
+
+    def run(self, dst_ptrs, src_ptrs, workspaces, streams):
+        """cutensorMgCopy; workspaces may be None when every size of the query is 0.  Returns the status."""
+        return cutensorMgCopy(self.h, self.plan, ptr_array(dst_ptrs), ptr_array(src_ptrs), ptr_array(workspaces) if workspaces is not None else None,
+                              None, ptr_array(streams))
+
+    def replay_on_host(self, dst_ptrs, src_ptrs):
+        """ctamdMgCopyReplayOnHost over host cell buffers (lists of addresses): the plan's launches, executed thread by thread."""
+        return lib.ctamdMgCopyReplayOnHost(self.plan, ptr_array(dst_ptrs), ptr_array(src_ptrs))
+
+    def close(self):
+        if self.plan:
+            check(cutensorMgDestroyCopyPlan(self.plan))
+            self.plan = ctypes.c_void_p()
+        if self.cd:
+            check(cutensorMgDestroyCopyDescriptor(self.cd))
+            self.cd = ctypes.c_void_p()
+        for d in self.descs:
+            check(cutensorMgDestroyTensorDescriptor(d))
+        self.descs = []
+        if self.h:
+            check(cutensorMgDestroy(self.h))
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def copy_plan(devices, dst, src, dtype=0):
+    """A CopyPlan for dst[dst["modes"]] = src[src["modes"]] on a handle over `devices` (see CopyPlan for the layout dicts)."""
+    return CopyPlan(devices, dst, src, dtype=dtype)
 
 
 def ptr_array(values):

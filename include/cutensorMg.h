@@ -78,6 +78,51 @@ cutensorStatus_t cutensorMgContraction(const cutensorMgHandle_t handle, const cu
                                        const void* C[], void* D[], void* workspaceDevice[], void* workspaceHost,
                                        cudaStream_t streams[]);
 
+/*
+ * Copy between block-cyclic layouts: dst[modesDst] = src[modesSrc] for every index of the valid index space, a pure copy with a
+ * permutation of modes (no scalar, no operator).  These declarations follow cuTENSORMg's public API; the reference tree never
+ * calls them, so no sample line pins them.
+ *
+ * Both tensors are block-cyclic as cutensorMgCreateTensorDescriptor defines them, with any block sizes, device counts, ragged
+ * extents and element / block strides on either side.  Elements of destination cells that belong to no valid index (padding of
+ * ragged extents, gaps of non-packed strides) are not written; source padding is never read into a valid element.  Overlapping
+ * source and destination cells are undefined.
+ *
+ * Accepted: fp16, bf16, fp32, fp64, both tensors of one type, up to 16 modes, positive strides, padded extents below 2^31.
+ * INVALID_VALUE: the label sets differ, a label's extent differs, a label is repeated in one tensor.  NOT_SUPPORTED: different
+ * data types, more than 16 modes, a destination cell on a device that is not in the handle (the launch that fills a cell runs on
+ * that cell's device and stream; source cells may live anywhere) and, at plan creation on a handle with real devices, a (source
+ * owner, destination device) pair without peer access: remote cells are read in place, and plan creation enables the peer mapping
+ * of exactly the pairs the plan reads across (a source device outside the handle included).  CUTENSOR_LOG_LEVEL=1 names the reason.
+ *
+ * Workspace: hostWorkspaceSize is 0; deviceWorkspaceSize[g] is 0 unless the source has, or handle device g owns, more than 128
+ * cells (the cell tables then go through the device workspace on that device's stream).  With all sizes 0 the call accepts null
+ * workspaces.  A too-small size at plan creation is INSUFFICIENT_WORKSPACE.
+ *
+ * cutensorMgCopy: ptrDst / ptrSrc have one entry per grid cell of the respective tensor, deviceWorkspace / streams one per handle
+ * device.  Asynchronous.  The call runs behind everything already enqueued on every stream of `streams`, and every stream of
+ * `streams` ends behind the call's last access to any cell (the fork / join of cutensorMgContraction): it does not matter which of
+ * the streams produced a source cell — one on a device outside the handle included — or goes on to use a cell.  deviceWorkspace[g],
+ * where its size is not 0, must be 8-byte aligned.  The plan must be used with the handle it was created on (INVALID_VALUE
+ * otherwise) but may outlive it until it is destroyed.
+ */
+typedef struct cutensorMgCopyDescriptor* cutensorMgCopyDescriptor_t;
+typedef struct cutensorMgCopyPlan*       cutensorMgCopyPlan_t;
+
+cutensorStatus_t cutensorMgCreateCopyDescriptor(const cutensorMgHandle_t handle, cutensorMgCopyDescriptor_t* desc,
+                                                const cutensorMgTensorDescriptor_t descDst, const int32_t modesDst[],
+                                                const cutensorMgTensorDescriptor_t descSrc, const int32_t modesSrc[]);
+cutensorStatus_t cutensorMgDestroyCopyDescriptor(cutensorMgCopyDescriptor_t desc);
+cutensorStatus_t cutensorMgCopyGetWorkspace(const cutensorMgHandle_t handle, const cutensorMgCopyDescriptor_t desc,
+                                            int64_t deviceWorkspaceSize[], int64_t* hostWorkspaceSize);
+cutensorStatus_t cutensorMgCreateCopyPlan(const cutensorMgHandle_t handle, cutensorMgCopyPlan_t* plan,
+                                          const cutensorMgCopyDescriptor_t desc,
+                                          const int64_t deviceWorkspaceSize[], int64_t hostWorkspaceSize);
+cutensorStatus_t cutensorMgDestroyCopyPlan(cutensorMgCopyPlan_t plan);
+cutensorStatus_t cutensorMgCopy(const cutensorMgHandle_t handle, const cutensorMgCopyPlan_t plan,
+                                void* ptrDst[], const void* ptrSrc[],
+                                void* deviceWorkspace[], void* hostWorkspace, cudaStream_t streams[]);
+
 #ifdef __cplusplus
 }
 #endif
