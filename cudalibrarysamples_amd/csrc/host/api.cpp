@@ -146,23 +146,6 @@ bool PlanMemoKey::operator==(const PlanMemoKey& o) const {
            std::memcmp(data, o.data, (size_t)used * sizeof(int64_t)) == 0;
 }
 
-namespace {
-
-double scalar_as_double(const void* s, hipDataType t) {   // real part for complex scalar types
-    if (s == nullptr) return 0.0;
-    return (t == HIP_R_64F || t == HIP_C_64F) ? *static_cast<const double*>(s) : (double)*static_cast<const float*>(s);
-}
-double scalar_imag(const void* s, hipDataType t) {
-    if (s == nullptr) return 0.0;
-    if (t == HIP_C_64F) return static_cast<const double*>(s)[1];
-    if (t == HIP_C_32F) return (double)static_cast<const float*>(s)[1];
-    return 0.0;
-}
-
-bool misaligned(const void* p, uint32_t a) { return a > 1 && (reinterpret_cast<uintptr_t>(p) % a) != 0; }
-
-}  // namespace
-
 // Incremental autotuning (contraction_plan_cache.cu:215-237): cutensorContract on a trial plan brackets its launches with
 // an event pair; the pairs are read here — at the next plan creation, before the cache is written, at handle destruction —
 // never inside cutensorContract, which stays asynchronous.  The fastest candidate seen so far is what the cache holds.
@@ -1583,8 +1566,8 @@ cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorP
     if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
     if (plan == nullptr || plan->kind != OpKind::Contraction) return CUTENSOR_STATUS_INVALID_VALUE;
     if (alpha == nullptr || beta == nullptr || A == nullptr || B == nullptr || D == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-    const CallScalars s{scalar_as_double(alpha, plan->scalarType), scalar_as_double(beta, plan->scalarType), scalar_imag(alpha, plan->scalarType),
-                        scalar_imag(beta, plan->scalarType)};
+    const CxScalar ca = read_scalar(alpha, plan->scalarType), cb = read_scalar(beta, plan->scalarType);
+    const CallScalars s{ca.re, cb.re, ca.im, cb.im};
     const bool betaZero = (s.b == 0.0 && s.bIm == 0.0);
     if (!betaZero && C == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
     if (misaligned(A, plan->alignA) || misaligned(B, plan->alignB) || misaligned(D, plan->alignD) ||
@@ -1645,172 +1628,6 @@ cutensorStatus_t cutensorContract(const cutensorHandle_t handle, const cutensorP
         }
     }
     if (err != hipSuccess) { CT_LOG("cutensorContract: %s", hipGetErrorString(err)); return CUTENSOR_STATUS_EXECUTION_FAILED; }
-    return CUTENSOR_STATUS_SUCCESS;
-} CTAMD_API_CATCH
-
-static hipError_t run_elementwise(const EwPlan& ew, hipDataType dtype, double a, const void* A, double g,
-                                  const void* C, void* D, hipStream_t stream, const void* E = nullptr, double d = 0.0,
-                                  double aIm = 0.0, double gIm = 0.0) {   // aIm / gIm: imaginary parts of alpha / gamma (complex data)
-    Ew2DParams p = ew.p;
-    p.A = A;
-    // a zero gamma drops the C term only for ADD (alpha perm(A) + 0): MUL / MAX / MIN still need it
-    p.C = (ew.usesC && (g != 0.0 || gIm != 0.0 || (p.opAC != 0 && p.opAC != CUTENSOR_OP_ADD))) ? C : nullptr;
-    p.D = D;
-    p.E = E;
-    p.alpha = (float)a; p.gamma = (float)g; p.alpha64 = a; p.gamma64 = g;
-    p.alphaIm = aIm; p.gammaIm = gIm;
-    p.delta = (float)d; p.delta64 = d;
-    // the block kernel moves elements and scales them, nothing else: under a unary operator the plan runs on the kernel its tiles were
-    // laid out for (same variant in the description, as for an attached operand)
-    const int variant = (ew.variant == EW_BLOCK && p.unA != 0) ? ew.blockFrom : ew.variant;
-    if (ew.converts()) return launch_elementwise_convert(p, variant, (int)ew.dtypeA, (int)ew.dtypeD, stream);
-    return launch_elementwise(p, variant, (int)dtype, stream);
-}
-
-// One launch of a complex trinary plan's pass (kernels/elementwise_trinary_cplx.hip): A on the tile path, X the second permuted operand
-// or nullptr, E the operand with D's strides or nullptr; complex scalars as (re, im).  C is dropped as run_elementwise drops it.
-struct CxScalar { double re, im; };
-static hipError_t run_trinary_cplx(const EwPlan& ew, hipDataType dtype, CxScalar a, const void* A, CxScalar x, const void* X, CxScalar d,
-                                   const void* E, CxScalar g, const void* C, void* D, hipStream_t stream) {
-    Ew2DParams p = ew.p;
-    p.A = A; p.X = X; p.E = E; p.D = D;
-    p.C = (ew.usesC && (g.re != 0.0 || g.im != 0.0 || (p.opAC != 0 && p.opAC != CUTENSOR_OP_ADD))) ? C : nullptr;
-    p.alpha = (float)a.re; p.alpha64 = a.re; p.alphaIm = a.im;
-    p.gamma = (float)g.re; p.gamma64 = g.re; p.gammaIm = g.im;
-    p.xi = (float)x.re; p.xi64 = x.re;
-    p.delta = (float)d.re; p.delta64 = d.re;
-    return launch_elementwise_trinary_cplx(p, x.im, d.im, ew.conjX, ew.conjE, ew.variant, (int)dtype, stream);
-}
-
-// reduction.cu:219-222, einsum.cu:369-372
-cutensorStatus_t cutensorReduce(const cutensorHandle_t handle, const cutensorPlan_t plan, const void* alpha,
-                                const void* A, const void* beta, const void* C, void* D, void* workspace,
-                                uint64_t workspaceSize, cudaStream_t stream) try {
-    if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
-    if (plan == nullptr || plan->kind != OpKind::Reduction) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (alpha == nullptr || beta == nullptr || A == nullptr || D == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-    const double a = scalar_as_double(alpha, plan->scalarType), b = scalar_as_double(beta, plan->scalarType);
-    const double aIm = scalar_imag(alpha, plan->scalarType), bIm = scalar_imag(beta, plan->scalarType);   // complex data: complex scalars
-    const bool betaSet = b != 0.0 || bIm != 0.0;
-    if (betaSet && C == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (misaligned(A, plan->alignA) || misaligned(D, plan->alignD) || (betaSet && misaligned(C, plan->alignC)))
-        return CUTENSOR_STATUS_INVALID_VALUE;
-    hipError_t err;
-    if (plan->red.isPermutation) {
-        err = run_elementwise(plan->red.perm, plan->dtype, a, A, b, C, D, stream, nullptr, 0.0, aIm, bIm);
-    } else {
-        if (plan->requiredWorkspace > 0 && (workspace == nullptr || workspaceSize < plan->requiredWorkspace))
-            return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;
-        ReduceParams p = plan->red.p;
-        p.A = A; p.C = betaSet ? C : D; p.D = D;
-        p.alpha = (float)a; p.beta = (float)b; p.alpha64 = a; p.beta64 = b;
-        p.alphaIm = aIm; p.betaIm = bIm;
-        p.partial = (p.splitR > 1) ? workspace : nullptr;
-        const bool acc64 = plan->accumulate64 || plan->dtype == HIP_R_64F;
-        err = launch_reduce(p, plan->red.variant, (int)plan->dtype, acc64, stream);
-        if (err == hipSuccess && p.splitR > 1) err = launch_reduce_finalize(p, (int)plan->dtype, acc64, stream);
-    }
-    if (err != hipSuccess) { CT_LOG("cutensorReduce: %s", hipGetErrorString(err)); return CUTENSOR_STATUS_EXECUTION_FAILED; }
-    return CUTENSOR_STATUS_SUCCESS;
-} CTAMD_API_CATCH
-
-// elementwise_permute.cu:198-200
-cutensorStatus_t cutensorPermute(const cutensorHandle_t handle, const cutensorPlan_t plan, const void* alpha,
-                                 const void* A, void* B, const cudaStream_t stream) try {
-    if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
-    if (plan == nullptr || plan->kind != OpKind::Permutation) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (alpha == nullptr || A == nullptr || B == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (misaligned(A, plan->alignA) || misaligned(B, plan->alignD)) return CUTENSOR_STATUS_INVALID_VALUE;
-    const double a = scalar_as_double(alpha, plan->scalarType);
-    hipError_t err = hipSuccess;
-    void* out = B;
-    if (plan->padFillElems != 0) {   // border (and interior, rewritten next) = padding value
-        // (border and offset in the OUTPUT's type: plan->dtype is A's, which a converting permutation tells apart)
-        err = launch_fill(B, plan->padFillElems, (int)plan->ew.dtypeD, plan->padValue, stream);
-        out = static_cast<char*>(B) + plan->padOffsetElems * (int64_t)dtype_size(plan->ew.dtypeD);
-    }
-    if (err == hipSuccess) err = run_elementwise(plan->ew, plan->dtype, a, A, 0.0, nullptr, out, stream, nullptr, 0.0, scalar_imag(alpha, plan->scalarType));
-    if (err != hipSuccess) { CT_LOG("cutensorPermute: %s", hipGetErrorString(err)); return CUTENSOR_STATUS_EXECUTION_FAILED; }
-    return CUTENSOR_STATUS_SUCCESS;
-} CTAMD_API_CATCH
-
-// elementwise_binary.cu:202-205
-cutensorStatus_t cutensorElementwiseBinaryExecute(const cutensorHandle_t handle, const cutensorPlan_t plan,
-                                                  const void* alpha, const void* A, const void* gamma,
-                                                  const void* C, void* D, cudaStream_t stream) try {
-    if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
-    if (plan == nullptr || plan->kind != OpKind::ElementwiseBinary) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (alpha == nullptr || gamma == nullptr || A == nullptr || C == nullptr || D == nullptr) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (misaligned(A, plan->alignA) || misaligned(C, plan->alignC) || misaligned(D, plan->alignD)) return CUTENSOR_STATUS_INVALID_VALUE;
-    const double a = scalar_as_double(alpha, plan->scalarType), g = scalar_as_double(gamma, plan->scalarType);
-    hipError_t err = run_elementwise(plan->ew, plan->dtype, a, A, g, C, D, stream, nullptr, 0.0, scalar_imag(alpha, plan->scalarType),
-                                     scalar_imag(gamma, plan->scalarType));
-    if (err != hipSuccess) return CUTENSOR_STATUS_EXECUTION_FAILED;
-    return CUTENSOR_STATUS_SUCCESS;
-} CTAMD_API_CATCH
-
-// elementwise_trinary.cu:223-227
-cutensorStatus_t cutensorElementwiseTrinaryExecute(const cutensorHandle_t handle, const cutensorPlan_t plan,
-                                                   const void* alpha, const void* A, const void* beta, const void* B,
-                                                   const void* gamma, const void* C, void* D, cudaStream_t stream) try {
-    if (handle == nullptr) return CUTENSOR_STATUS_NOT_INITIALIZED;
-    if (plan == nullptr || plan->kind != OpKind::ElementwiseTrinary) return CUTENSOR_STATUS_INVALID_VALUE;
-    if (alpha == nullptr || beta == nullptr || gamma == nullptr || A == nullptr || B == nullptr || C == nullptr || D == nullptr)
-        return CUTENSOR_STATUS_INVALID_VALUE;
-    if (misaligned(A, plan->alignA) || misaligned(B, plan->alignB3) || misaligned(C, plan->alignC) || misaligned(D, plan->alignD))
-        return CUTENSOR_STATUS_INVALID_VALUE;
-    const double a = scalar_as_double(alpha, plan->scalarType), b = scalar_as_double(beta, plan->scalarType),
-                 g = scalar_as_double(gamma, plan->scalarType);
-    const EwTrinaryPlan& t = plan->ew3;
-    hipError_t err = hipSuccess;
-    if (plan->dtype == HIP_C_32F || plan->dtype == HIP_C_64F) {
-        // complex data: the same forms, every launch that carries an E or X operand on the complex trinary kernels
-        const CxScalar ca{a, scalar_imag(alpha, plan->scalarType)}, cb{b, scalar_imag(beta, plan->scalarType)},
-                       cg{g, scalar_imag(gamma, plan->scalarType)}, none{0.0, 0.0}, one{1.0, 0.0};
-        if (t.bothPermuted) {
-            err = run_trinary_cplx(t.last, plan->dtype, ca, A, cb, B, none, nullptr, cg, C, D, stream);
-        } else if (t.twoPass) {
-            const uintptr_t c = reinterpret_cast<uintptr_t>(C), d = reinterpret_cast<uintptr_t>(D);
-            const bool readsC = t.last.usesC && (cg.re != 0.0 || cg.im != 0.0 || (t.last.p.opAC != 0 && t.last.p.opAC != CUTENSOR_OP_ADD));
-            if (readsC && c < d + t.spanD && d < c + t.spanC) {      // C overlaps D: the single gather launch, as for real data
-                if (!t.hasGather) return CUTENSOR_STATUS_NOT_SUPPORTED;
-                err = run_trinary_cplx(t.gather, plan->dtype, ca, A, cb, B, none, nullptr, cg, C, D, stream);
-            } else {
-                err = run_elementwise(t.first, plan->dtype, ca.re, A, 0.0, nullptr, D, stream, nullptr, 0.0, ca.im);          // D = alpha cj(perm A)
-                if (err == hipSuccess) err = run_trinary_cplx(t.last, plan->dtype, cb, B, none, nullptr, one, D, cg, C, D, stream);   // in place, E = D
-            }
-        } else if (t.swapAB) {
-            err = run_trinary_cplx(t.last, plan->dtype, ca, A, none, nullptr, cb, B, cg, C, D, stream);   // E = B
-        } else {
-            err = run_trinary_cplx(t.last, plan->dtype, cb, B, none, nullptr, ca, A, cg, C, D, stream);   // E = A
-        }
-    } else if (t.bothPermuted) {
-        Ew2DParams q = t.last.p;
-        q.A = A; q.X = B; q.D = D; q.E = nullptr;
-        q.C = (t.last.usesC && (g != 0.0 || (q.opAC != 0 && q.opAC != CUTENSOR_OP_ADD))) ? C : nullptr;
-        q.alpha = (float)a; q.alpha64 = a; q.xi = (float)b; q.xi64 = b; q.gamma = (float)g; q.gamma64 = g;
-        err = launch_elementwise(q, t.last.variant, (int)plan->dtype, stream);
-    } else if (t.twoPass) {
-        // C inside D's range (in-place use: C == D) and read by the last pass: pass 1 would overwrite it first.  One launch of the
-        // element-gather kernel instead — a lane reads its element of C before it writes that element of D.
-        const uintptr_t c = reinterpret_cast<uintptr_t>(C), d = reinterpret_cast<uintptr_t>(D);
-        const bool readsC = t.last.usesC && (g != 0.0 || (t.last.p.opAC != 0 && t.last.p.opAC != CUTENSOR_OP_ADD));
-        if (readsC && c < d + t.spanD && d < c + t.spanC) {
-            if (!t.hasGather) return CUTENSOR_STATUS_NOT_SUPPORTED;   // (more unfusable modes than the single launch describes)
-            Ew2DParams q = t.gather.p;
-            q.A = A; q.X = B; q.C = C; q.D = D; q.E = nullptr;
-            q.alpha = (float)a; q.alpha64 = a; q.xi = (float)b; q.xi64 = b; q.gamma = (float)g; q.gamma64 = g;
-            err = launch_elementwise(q, EW_GENERIC, (int)plan->dtype, stream);
-        } else {
-            err = run_elementwise(t.first, plan->dtype, a, A, 0.0, nullptr, D, stream);                       // D = alpha perm(A)
-            if (err == hipSuccess) err = run_elementwise(t.last, plan->dtype, b, B, g, C, D, stream, D, 1.0);  // combine in place
-        }
-    } else if (t.swapAB) {
-        err = run_elementwise(t.last, plan->dtype, a, A, g, C, D, stream, B, b);   // E = B (has D's layout)
-    } else {
-        err = run_elementwise(t.last, plan->dtype, b, B, g, C, D, stream, A, a);   // E = A
-    }
-    if (err != hipSuccess) { CT_LOG("cutensorElementwiseTrinaryExecute: %s", hipGetErrorString(err)); return CUTENSOR_STATUS_EXECUTION_FAILED; }
     return CUTENSOR_STATUS_SUCCESS;
 } CTAMD_API_CATCH
 
@@ -1933,14 +1750,6 @@ void ctamdPlanMemoStats(const cutensorHandle_t handle, uint64_t* hits, uint64_t*
 // buf holds n characters of a plan's own keys, `{"key":..,"key":..,` — the keys of its inner plan follow: the inner plan's description is
 // written over the trailing ',' and its '{' turned into that ','
 static int describe_inner(const cutensorPlan& plan, char* buf, size_t len, int n);
-// A plan of the element-wise or reduction family whose operands carry a unary operator other than IDENTITY / CONJ: the closing '}' of the
-// description in buf[0, n) becomes ,"unary":[opA, opB, opC]} (cutensorOperator_t values, IDENTITY where there is none).  Every other
-// description stays as it is.
-static int describe_unary(char* buf, size_t len, int n, int32_t a, int32_t b, int32_t c) {
-    if ((a == 0 && b == 0 && c == 0) || n <= 0 || (size_t)n >= len || buf[n - 1] != '}') return n;
-    auto code = [](int32_t u) { return u == 0 ? (int)CUTENSOR_OP_IDENTITY : (int)u; };
-    return n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"unary\":[%d,%d,%d]}", code(a), code(b), code(c));
-}
 // Writes a one-line JSON description of the plan's kernel choice into buf.
 int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
     if (plan == nullptr || buf == nullptr || len == 0) return -1;
@@ -2014,43 +1823,8 @@ int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len) try {
             n += std::snprintf(buf + n, len - n, "%s[%lld,%lld,%lld]", i ? "," : "", (long long)plan->view.K[i].extent,
                                (long long)plan->view.K[i].sA, (long long)plan->view.K[i].sB);
         if (n > 0 && (size_t)n < len) n += std::snprintf(buf + n, len - n, "]}");
-    } else if (plan->kind == OpKind::Reduction && !plan->red.isPermutation) {
-        n = std::snprintf(buf, len, "{\"op\":\"reduction\",\"variant\":%d,\"kept\":%u,\"red\":%u,\"splitR\":%u,\"redPerSplit\":%u,\"rowAny\":%u,\"workspace\":%llu}",
-                          plan->red.variant, plan->red.p.kept.total, plan->red.p.red.total, plan->red.p.splitR, plan->red.p.redPerSplit,
-                          plan->red.p.rowAny, (unsigned long long)plan->requiredWorkspace);
-        n = describe_unary(buf, len, n, plan->red.p.unA, 0, plan->red.p.unC);
-    } else if (plan->kind == OpKind::ElementwiseTrinary) {
-        // the three forms (plan_elementwise_trinary): one pass with E, one pass with two tiles, two passes (variant_first: pass 1's kernel;
-        // variant_inplace: the single launch that replaces both passes when C overlaps D, -1 if there is none).  "op" stays "elementwise",
-        // as for every plan of the element-wise family; "form" tells the trinary plans from the others
-        const EwTrinaryPlan& t = plan->ew3;
-        n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"form\":\"trinary\",\"passes\":%d,\"bothPermuted\":%d,\"swapAB\":%d,\"variant\":%d,\"variant_first\":%d,"
-                          "\"variant_inplace\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u}",
-                          t.twoPass ? 2 : 1, (int)t.bothPermuted, (int)t.swapAB, t.last.variant, t.twoPass ? t.first.variant : -1,
-                          t.hasGather ? t.gather.variant : -1, t.last.p.E0, t.last.p.E1, t.last.p.rest.total, t.last.p.nBlocks, t.last.p.tile0);
-        // each operand's operator, read back from the role its form gave it
-        const Ew2DParams& q = t.last.p;
-        const int32_t uA = t.bothPermuted ? q.unA : t.twoPass ? t.first.p.unA : t.swapAB ? q.unA : q.unE;
-        const int32_t uB = t.bothPermuted ? q.unX : t.twoPass ? q.unA : t.swapAB ? q.unE : q.unA;
-        n = describe_unary(buf, len, n, uA, uB, q.unC);
-        // complex plans: each operand's conjugation, read back the same way
-        if ((plan->dtype == HIP_C_32F || plan->dtype == HIP_C_64F) && n > 1 && (size_t)n < len && buf[n - 1] == '}') {
-            const int cA = t.bothPermuted ? q.conjA : t.twoPass ? t.first.p.conjA : t.swapAB ? q.conjA : t.last.conjE;
-            const int cB = t.bothPermuted ? t.last.conjX : t.twoPass ? q.conjA : t.swapAB ? t.last.conjE : q.conjA;
-            n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"conj\":[%d,%d,%d]}", cA, cB, (int)q.conjC);
-        }
     } else {
-        const EwPlan& e = (plan->kind == OpKind::Reduction) ? plan->red.perm : plan->ew;
-        n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u,\"order\":%u}",
-                          e.variant, e.p.E0, e.p.E1, e.p.rest.total, e.p.nBlocks, e.p.tile0, e.p.order);
-        n = describe_unary(buf, len, n, e.p.unA, 0, e.p.unC);
-        // a converting plan (kernels/elementwise_convert.hip): the hipDataType values of A and of D
-        if (e.converts() && n > 1 && (size_t)n < len && buf[n - 1] == '}')
-            n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"convert\":[%d,%d]}", (int)e.dtypeA, (int)e.dtypeD);
-        // a padded permutation: the elements the fill writes (the whole padded buffer) and the element offset of the interior, beside the inner plan's fields
-        if (plan->kind == OpKind::Permutation && plan->padFillElems != 0 && n > 1 && (size_t)n < len && buf[n - 1] == '}')
-            n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"pad\":[%llu,%lld]}", (unsigned long long)plan->padFillElems,
-                                      (long long)plan->padOffsetElems);
+        n = describe_elementwise(*plan, buf, len);   // element-wise and reduction plans (exec_elementwise.cpp)
     }
     return n;
 } CTAMD_API_CATCH_INT

@@ -177,7 +177,8 @@ struct EwPlan {
     hipDataType dtypeA = HIP_R_32F, dtypeD = HIP_R_32F;
     bool converts() const { return dtypeA != dtypeD; }
     // complex trinary plans (kernels/elementwise_trinary_cplx.hip): conjugation of the second permuted operand X and of the operand that
-    // rides along as E — Ew2DParams, the argument block of the other kernels, has no field for either
+    // rides along as E — Ew2DParams, the argument block of the other kernels, has no field for either (run_elementwise hands them over
+    // in an Ew3CplxExtras)
     int32_t    conjX = 0, conjE = 0;
 };
 // cutensorElementwiseTrinaryExecute: D = opABC(opAB(alpha A, beta B), gamma C) as one or two passes of the
@@ -209,6 +210,24 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
 cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op, EwTrinaryPlan& plan, std::string* why);
 cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t wsLimit, int numCUs,
                                 ReducePlan& plan, std::string* why);
+
+// ---- execute (exec_elementwise.cpp: the entry points of this family and the one path from a plan to a launch) ----------------
+struct CxScalar { double re = 0.0, im = 0.0; };
+inline CxScalar read_scalar(const void* s, hipDataType t) {   // a caller's alpha / beta / gamma of scalar type t (real types: im = 0)
+    if (s == nullptr) return {};
+    auto part = [&](int i) { return (t == HIP_R_64F || t == HIP_C_64F) ? static_cast<const double*>(s)[i] : (double)static_cast<const float*>(s)[i]; };
+    return {part(0), (t == HIP_C_32F || t == HIP_C_64F) ? part(1) : 0.0};
+}
+inline bool misaligned(const void* p, uint32_t a) { return a > 1 && (reinterpret_cast<uintptr_t>(p) % a) != 0; }
+// One launch of an element-wise plan: the operands by role, each with its scalar — A through the tile path (alpha), X the second
+// permuted operand (xi), E the operand with D's strides (delta), C (gamma); a role without an operand stays null
+struct EwCall {
+    const void *A = nullptr, *X = nullptr, *E = nullptr, *C = nullptr;
+    void*       D = nullptr;
+    CxScalar    alpha, xi, delta, gamma;
+};
+hipError_t run_elementwise(const EwPlan& ew, hipDataType dtype, const EwCall& call, hipStream_t stream);
+int describe_elementwise(const cutensorPlan& pl, char* buf, size_t len);   // ctamdDescribePlan of an element-wise or reduction plan
 
 // Raised while the pairwise plans of a trinary or a block-sparse contraction are made or priced: under COMPUTE_DESC_32F on fp64 /
 // complex128 data those keep the fp64 kernels (f64x_decide, contraction_route.cpp), and the plan memo stands aside for them

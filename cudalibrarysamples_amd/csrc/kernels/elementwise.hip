@@ -51,18 +51,6 @@ __device__ __forceinline__ f32x4 ew_comb4(int op, f32x4 x, f32x4 y) {
     return r;
 }
 
-// offset of a rest index in the second permuted operand X (explicit stride array, same digits as rest_offsets)
-__device__ __forceinline__ int64_t rest_offset_x(const ModeGroup& g, const int64_t* sx, uint32_t idx) {
-    int64_t o = 0;
-#pragma unroll
-    for (int i = 0; i < kMaxGroupModes; ++i) {
-        const uint32_t q = __umulhi(idx, g.div[i].magic) >> g.div[i].shift;
-        o += (int64_t)(idx - q * g.div[i].d) * sx[i];
-        idx = q;
-    }
-    return o;
-}
-
 // ---------------------------------------------------------------------------------------------
 // EW_TRANSPOSE (fp32): requires sD0 == 1, sA1 == 1, E0 % 4 == 0, E1 % 4 == 0, every other stride
 // a multiple of 4 elements and 16-byte aligned bases.
@@ -245,15 +233,9 @@ __global__ void __launch_bounds__(256) ew_block_kernel(const Ew2DParams p) {
 // One (re, im) pair per lane: 8- / 16-byte loads and stores, 512 B / 1 KiB per wave along D's fastest mode.  Same tile
 // decomposition as ew_generic_kernel (64 dim0 elements x 4 dim1 rows).  HBM-bound: 2 |D| bytes (+ |C|).
 // ---------------------------------------------------------------------------------------------
-template <typename R> struct EwCx { R re, im; };
-template <typename R> __device__ __forceinline__ EwCx<R> cx_mul(EwCx<R> a, EwCx<R> b) { return EwCx<R>{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-template <typename R> __device__ __forceinline__ EwCx<R> cx_comb(int op, EwCx<R> x, EwCx<R> y) {
-    return op == 5 ? cx_mul(x, y) : EwCx<R>{x.re + y.re, x.im + y.im};     // CUTENSOR_OP_MUL, else ADD (the planner admits nothing else)
-}
-
 template <typename R>
 __global__ void __launch_bounds__(256) ew_generic_cplx_kernel(const Ew2DParams p) {
-    typedef EwCx<R> T;
+    typedef WCx<R> T;                 // (re, im) pairs and their arithmetic: wide_elem.h
     const T* A = static_cast<const T*>(p.A);
     const T* C = static_cast<const T*>(p.C);
     T*       D = static_cast<T*>(p.D);
@@ -268,11 +250,11 @@ __global__ void __launch_bounds__(256) ew_generic_cplx_kernel(const Ew2DParams p
         if (c0 >= p.E0 || r1 >= p.E1) continue;
         T a = A[oA + (int64_t)c0 * p.sA0 + (int64_t)r1 * p.sA1];
         if (p.conjA) a.im = -a.im;
-        T v = cx_mul(alpha, a);
+        T v = wcx_mul(alpha, a);
         if (C != nullptr) {
             T c = C[oC + (int64_t)c0 * p.sC0 + (int64_t)r1 * p.sC1];
             if (p.conjC) c.im = -c.im;
-            v = cx_comb(p.opAC, v, cx_mul(gamma, c));
+            v = WCplx<R>::apply(p.opAC, v, wcx_mul(gamma, c));     // MUL, else ADD (the planner admits nothing else)
         }
         D[oD + (int64_t)c0 * p.sD0 + (int64_t)r1 * p.sD1] = v;
     }
@@ -432,38 +414,30 @@ hipError_t launch_elementwise(const Ew2DParams& p, int variant, int dtype, hipSt
         }
         variant = EW_GENERIC;
     }
+    const unsigned grid = ew_tiled_grid(p, variant);
     if (variant == EW_TRANSPOSE_ANY) {
         if (p.E != nullptr || p.X != nullptr) return hipErrorInvalidValue;   // (planned for permutations and the binary form only)
-        unsigned g = p.nBlocks < (1u << 22) ? p.nBlocks : (1u << 22);
         if (p.C != nullptr) {
             switch (dtype) {
-                case HIP_R_32F:  CTAMD_EW_TWIN(un, g, (ew_transpose_any_kernel<float, true>), (ew_transpose_any_un_kernel<float, true>)); return hipGetLastError();
-                case HIP_R_16F:  CTAMD_EW_TWIN(un, g, (ew_transpose_any_kernel<__half, true>), (ew_transpose_any_un_kernel<__half, true>)); return hipGetLastError();
-                case HIP_R_16BF: CTAMD_EW_TWIN(un, g, (ew_transpose_any_kernel<__hip_bfloat16, true>), (ew_transpose_any_un_kernel<__hip_bfloat16, true>)); return hipGetLastError();
+                case HIP_R_32F:  CTAMD_EW_TWIN(un, grid, (ew_transpose_any_kernel<float, true>), (ew_transpose_any_un_kernel<float, true>)); return hipGetLastError();
+                case HIP_R_16F:  CTAMD_EW_TWIN(un, grid, (ew_transpose_any_kernel<__half, true>), (ew_transpose_any_un_kernel<__half, true>)); return hipGetLastError();
+                case HIP_R_16BF: CTAMD_EW_TWIN(un, grid, (ew_transpose_any_kernel<__hip_bfloat16, true>), (ew_transpose_any_un_kernel<__hip_bfloat16, true>)); return hipGetLastError();
                 default: return hipErrorInvalidValue;
             }
         }
         if (p.tile0 == 128u && (dtype == HIP_R_16F || dtype == HIP_R_16BF)) {     // the pair form (planned for even extents / strides)
             if (((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.D)) & 3u) != 0u) return hipErrorInvalidValue;
-            if (dtype == HIP_R_16F) CTAMD_EW_TWIN(un, g, ew_transpose_any_pair_kernel<__half>, ew_transpose_any_pair_un_kernel<__half>);
-            else                    CTAMD_EW_TWIN(un, g, ew_transpose_any_pair_kernel<__hip_bfloat16>, ew_transpose_any_pair_un_kernel<__hip_bfloat16>);
+            if (dtype == HIP_R_16F) CTAMD_EW_TWIN(un, grid, ew_transpose_any_pair_kernel<__half>, ew_transpose_any_pair_un_kernel<__half>);
+            else                    CTAMD_EW_TWIN(un, grid, ew_transpose_any_pair_kernel<__hip_bfloat16>, ew_transpose_any_pair_un_kernel<__hip_bfloat16>);
             return hipGetLastError();
         }
         switch (dtype) {
-            case HIP_R_32F:  CTAMD_EW_TWIN(un, g, (ew_transpose_any_kernel<float, false>), (ew_transpose_any_un_kernel<float, false>)); return hipGetLastError();
-            case HIP_R_16F:  CTAMD_EW_TWIN(un, g, (ew_transpose_any_kernel<__half, false>), (ew_transpose_any_un_kernel<__half, false>)); return hipGetLastError();
-            case HIP_R_16BF: CTAMD_EW_TWIN(un, g, (ew_transpose_any_kernel<__hip_bfloat16, false>), (ew_transpose_any_un_kernel<__hip_bfloat16, false>)); return hipGetLastError();
+            case HIP_R_32F:  CTAMD_EW_TWIN(un, grid, (ew_transpose_any_kernel<float, false>), (ew_transpose_any_un_kernel<float, false>)); return hipGetLastError();
+            case HIP_R_16F:  CTAMD_EW_TWIN(un, grid, (ew_transpose_any_kernel<__half, false>), (ew_transpose_any_un_kernel<__half, false>)); return hipGetLastError();
+            case HIP_R_16BF: CTAMD_EW_TWIN(un, grid, (ew_transpose_any_kernel<__hip_bfloat16, false>), (ew_transpose_any_un_kernel<__hip_bfloat16, false>)); return hipGetLastError();
             default: return hipErrorInvalidValue;
         }
     }
-    // One workgroup per tile: a workgroup that loops over tiles serialises its own read -> barrier -> write phases, fresh
-    // workgroups overlap them across the CU (2048^3 permutation, 64 x 64 tiles: 5.37 TB/s with the grid capped at 32 Ki
-    // workgroups, 6.09-6.14 with one workgroup per tile; profiles/r03_transpose_sweep*.jsonl).  The grid-stride loop stays
-    // for tensors beyond 2^22 tiles.
-    unsigned grid = p.nBlocks;
-    const unsigned cap = 1u << 22;
-    if (variant == EW_TRANSPOSE && p.order) grid = 8u * p.idsPerXcd;
-    if (grid > cap) grid = cap;
     if (variant == EW_TRANSPOSE && dtype == HIP_R_32F) {
         if (p.X != nullptr) {
             if (p.tile0 == 128) CTAMD_EW_TWIN(un, grid, (ew_transpose_f32_kernel<true, 128>), (ew_transpose_f32_un_kernel<true, 128>));

@@ -1,4 +1,5 @@
-// elementwise_common.h — device helpers shared by the element-wise translation units (elementwise.hip and elementwise_convert.hip):
+// elementwise_common.h — device helpers shared by the element-wise translation units (elementwise.hip, elementwise_convert.hip and
+// elementwise_trinary_cplx.hip):
 // the fast division, the offsets of a rest index, the tile decomposition with its two tile orders, the binary combiners and the
 // conversions between 16-bit storage and fp32.  Moved here unchanged from elementwise.hip when the converting kernels arrived.
 #pragma once
@@ -26,6 +27,18 @@ __device__ __forceinline__ void rest_offsets(const ModeGroup& g, uint32_t idx, i
         oC += (int64_t)digit * g.stride[2][i];
         idx = q;
     }
+}
+
+// offset of a rest index in the second permuted operand X (explicit stride array, same digits as rest_offsets)
+__device__ __forceinline__ int64_t rest_offset_x(const ModeGroup& g, const int64_t* sx, uint32_t idx) {
+    int64_t o = 0;
+#pragma unroll
+    for (int i = 0; i < kMaxGroupModes; ++i) {
+        const uint32_t q = __umulhi(idx, g.div[i].magic) >> g.div[i].shift;
+        o += (int64_t)(idx - q * g.div[i].d) * sx[i];
+        idx = q;
+    }
+    return o;
 }
 
 // binary combiners of the element-wise family (cutensorOperator_t values; 0 = ADD)

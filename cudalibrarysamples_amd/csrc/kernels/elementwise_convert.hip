@@ -347,10 +347,7 @@ static hipError_t launch_cv_tile(const Ew2DParams& p, unsigned grid, hipStream_t
 template <class KA, class KD, bool HASC, bool UN>
 static hipError_t launch_cv(const Ew2DParams& p, int variant, hipStream_t stream) {
     constexpr uint32_t LV = (uint32_t)CvPair<KA, KD>::LV;
-    // one workgroup per tile (elementwise.hip, launch_elementwise); the grid-stride loops serve tensors beyond 2^22 tiles
-    unsigned grid = p.nBlocks;
-    if (variant == EW_TRANSPOSE && p.order) grid = 8u * p.idsPerXcd;
-    if (grid > (1u << 22)) grid = 1u << 22;
+    const unsigned grid = ew_tiled_grid(p, variant);
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.D) | (HASC ? reinterpret_cast<uintptr_t>(p.C) : 0);
     if (variant == EW_TRANSPOSE) {
         if ((ptrs & 15u) != 0u || p.tile1 != (uint32_t)CV_T1 || p.E0 % LV != 0u || p.E1 % LV != 0u) return hipErrorInvalidValue;

@@ -42,18 +42,6 @@ struct Ew3CplxParams {
     int32_t    conjX, conjE;
 };
 
-// offset of a rest index in X (Ew2DParams::restX, same digits as rest_offsets)
-__device__ __forceinline__ int64_t c3_rest_offset_x(const ModeGroup& g, const int64_t* sx, uint32_t idx) {
-    int64_t o = 0;
-#pragma unroll
-    for (int i = 0; i < kMaxGroupModes; ++i) {
-        const uint32_t q = __umulhi(idx, g.div[i].magic) >> g.div[i].shift;
-        o += (int64_t)(idx - q * g.div[i].d) * sx[i];
-        idx = q;
-    }
-    return o;
-}
-
 // v = alpha * a, then X, E and C join in that order (the order of the real kernels, elementwise_kernels.inc)
 template <class Tr, bool HASX>
 __device__ __forceinline__ typename Tr::Acc c3_finish(const Ew3CplxParams& q, typename Tr::Acc a, typename Tr::Acc x, typename Tr::Acc e, bool hasE,
@@ -122,7 +110,7 @@ __global__ void __launch_bounds__(256) ew3c_transpose_kernel(const Ew3CplxParams
                 }
             }
             if constexpr (HASX) {
-                const int64_t oX = c3_rest_offset_x(p.rest, p.restX, t.rest);
+                const int64_t oX = rest_offset_x(p.rest, p.restX, t.rest);
 #pragma unroll
                 for (int ps = 0; ps < RD_PASSES; ++ps) {
                     const uint32_t r0 = i0 + NV * (tid / LPR) + RPP * ps;
@@ -264,7 +252,7 @@ __global__ void __launch_bounds__(256) ew3c_generic_kernel(const Ew3CplxParams q
         const int64_t offD = oD + (int64_t)c0 * p.sD0 + (int64_t)r1 * p.sD1;
         Acc a = Tr::load1(A + oA + (int64_t)c0 * p.sA0 + (int64_t)r1 * p.sA1, p.conjA != 0);
         Acc x = a, e = a, c = a;
-        if (X != nullptr) x = Tr::load1(X + c3_rest_offset_x(p.rest, p.restX, t.rest) + (int64_t)c0 * p.sX0 + (int64_t)r1 * p.sX1, q.conjX != 0);
+        if (X != nullptr) x = Tr::load1(X + rest_offset_x(p.rest, p.restX, t.rest) + (int64_t)c0 * p.sX0 + (int64_t)r1 * p.sX1, q.conjX != 0);
         if (E != nullptr) e = Tr::load1(E + offD, q.conjE != 0);
         if (C != nullptr) c = Tr::load1(C + oC + (int64_t)c0 * p.sC0 + (int64_t)r1 * p.sC1, p.conjC != 0);
         Acc v = Tr::scale(p.alpha64, p.alphaIm, a);
@@ -279,10 +267,7 @@ __global__ void __launch_bounds__(256) ew3c_generic_kernel(const Ew3CplxParams q
 template <class Tr, int T0, int T1, int TX0, int TX1>
 static hipError_t launch_c3(const Ew3CplxParams& q, int variant, hipStream_t stream) {
     const Ew2DParams& p = q.p;
-    unsigned grid = p.nBlocks;
-    const unsigned cap = 1u << 22;                   // one workgroup per tile (elementwise.hip, launch_elementwise); beyond that the grid-stride loops
-    if (variant == EW_TRANSPOSE && p.order) grid = 8u * p.idsPerXcd;
-    if (grid > cap) grid = cap;
+    const unsigned grid = ew_tiled_grid(p, variant);
     if (variant == EW_TRANSPOSE || variant == EW_ROWCOPY) {
         // 16-byte lanes: what the planner derived from the descriptors' alignments is checked on the pointers once more
         uintptr_t bits = reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.D) | reinterpret_cast<uintptr_t>(p.E) |
@@ -306,14 +291,10 @@ static hipError_t launch_c3(const Ew3CplxParams& q, int variant, hipStream_t str
     return hipGetLastError();
 }
 
-hipError_t launch_elementwise_trinary_cplx(const Ew2DParams& p, double xiIm, double deltaIm, int conjX, int conjE, int variant, int dtype,
-                                           hipStream_t stream) {
+hipError_t launch_elementwise_trinary_cplx(const Ew2DParams& p, const Ew3CplxExtras& x, int variant, int dtype, hipStream_t stream) {
     if (p.nBlocks == 0) return hipSuccess;
     if (p.unA != 0 || p.unX != 0 || p.unE != 0 || p.unC != 0) return hipErrorInvalidValue;   // (complex data takes IDENTITY and CONJ only)
-    Ew3CplxParams q;
-    q.p = p;
-    q.xiIm = xiIm; q.deltaIm = deltaIm;
-    q.conjX = conjX; q.conjE = conjE;
+    const Ew3CplxParams q{p, x.xiIm, x.deltaIm, x.conjX, x.conjE};
     if (dtype == HIP_C_32F) return launch_c3<WCplx<float>, 128, 32, 64, 64>(q, variant, stream);
     if (dtype == HIP_C_64F) return launch_c3<WCplx<double>, 64, 32, 64, 32>(q, variant, stream);
     return hipErrorInvalidValue;

@@ -126,15 +126,26 @@ enum EwVariant : int {
     EW_BLOCK     = 3   // pure permutation of 2- / 4-byte elements whose leading modes are the same packed set in A and D: contiguous blocks
                        // through LDS, permuted inside (Ew2DParams::blk*); falls back to EW_GENERIC when a C / E / X operand is attached
 };
+// Grid of a tiled element-wise launch.  One workgroup per tile: a workgroup that loops over tiles serialises its own read -> barrier ->
+// write phases, fresh workgroups overlap them across the CU (2048^3 permutation, 64 x 64 tiles: 5.37 TB/s with the grid capped at 32 Ki
+// workgroups, 6.09-6.14 with one workgroup per tile; profiles/r03_transpose_sweep*.jsonl).  Under tile order 1 the transposing kernels
+// walk 8 * idsPerXcd ids; the grid-stride loops stay for tensors beyond 2^22 tiles.
+inline unsigned ew_tiled_grid(const Ew2DParams& p, int variant) {
+    const unsigned grid = (variant == EW_TRANSPOSE && p.order) ? 8u * p.idsPerXcd : p.nBlocks;
+    return grid > (1u << 22) ? (1u << 22) : grid;
+}
 hipError_t launch_elementwise(const Ew2DParams& p, int variant, int dtype, hipStream_t stream);
 // the converting kernels (elementwise_convert.hip): A of dtypeA, D and C of dtypeD — bf16 / fp16 <-> fp32 and fp32 <-> fp64; variants
 // EW_TRANSPOSE / EW_ROWCOPY / EW_GENERIC with a lane of 16 / min(sizeof A, sizeof D) elements; any other pair or variant is an error
 hipError_t launch_elementwise_convert(const Ew2DParams& p, int variant, int dtypeA, int dtypeD, hipStream_t stream);
 // the complex trinary kernels (elementwise_trinary_cplx.hip): complex64 / complex128 data with an E and / or X operand attached; variants
 // EW_TRANSPOSE / EW_ROWCOPY / EW_GENERIC.  p carries the scalars' other parts (alpha64 / alphaIm, gamma64 / gammaIm, xi64, delta64) and
-// conjA / conjC; xiIm / deltaIm / conjX / conjE are what Ew2DParams has no field for
-hipError_t launch_elementwise_trinary_cplx(const Ew2DParams& p, double xiIm, double deltaIm, int conjX, int conjE, int variant, int dtype,
-                                           hipStream_t stream);
+// conjA / conjC; Ew3CplxExtras is what Ew2DParams has no field for
+struct Ew3CplxExtras {
+    double  xiIm = 0.0, deltaIm = 0.0;   // imaginary parts of xi (X's scalar) and delta (E's scalar)
+    int32_t conjX = 0, conjE = 0;
+};
+hipError_t launch_elementwise_trinary_cplx(const Ew2DParams& p, const Ew3CplxExtras& x, int variant, int dtype, hipStream_t stream);
 // D[0 .. n) = value (contiguous; the padded-permutation border fill)
 hipError_t launch_fill(void* D, uint64_t n, int dtype, double value, hipStream_t stream);
 

@@ -186,11 +186,12 @@ struct SplitKReduceParams {
 // form of cutensorReduce):  D = alpha * perm(A) [+ gamma * perm(C)].
 // The planner picks two "tile" modes — dim0 = D's fastest mode, dim1 = A's fastest mode (or D's
 // second mode when A and D share the fastest one) — and linearises all remaining modes into
-// `rest`.  A workgroup owns one T0 x T1 tile of one rest index.
+// `rest`.  A workgroup owns one T0 x T1 tile of one rest index.  Pointers and scalars are written per
+// launch, all of them in one place (host/exec_elementwise.cpp, run_elementwise).
 // ---------------------------------------------------------------------------------------------
 struct Ew2DParams {
     const void* A;
-    const void* C;                 // may be nullptr (gamma == 0)
+    const void* C;                 // may be nullptr (C is not read: gamma == 0 under ADD)
     void*       D;
     uint32_t    E0, E1;            // extents of the two tile modes (E1 = 1 when there is none)
     int64_t     sA0, sA1, sD0, sD1, sC0, sC1;
