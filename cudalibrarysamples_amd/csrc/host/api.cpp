@@ -1702,7 +1702,7 @@ size_t cutensorGetVersion(void) { return CUTENSOR_VERSION; }
 // A contraction plan that fell to the mode-table kernel because a group has more unfusable modes than the tiled kernels'
 // argument block describes: its canonical modes as (group 0 = L, 1 = M, 2 = N, 3 = K; caller's label; extent), at most maxOut of
 // them; returns how many there are, 0 for every other plan.  cuTENSORMg uses it to peel one digit of an oversized group into a
-// host loop (mg.cpp) instead of running the functional kernel.
+// host loop (mg/mg_contraction_plan.cpp) instead of running the functional kernel.
 int ctamdPlanModeTableGroups(const cutensorPlan_t plan, int32_t* group, int32_t* label, int64_t* extent, int maxOut) try {
     if (plan == nullptr || plan->kind != OpKind::Contraction || plan->planKind != PlanKind::ModeTable) return 0;
     if (plan->view.dtype == HIP_C_32F || plan->view.dtype == HIP_C_64F) return 0;     // complex data: not a matter of mode counts

@@ -1,6 +1,6 @@
 // Device code of libcutensorMg.so (gfx950): the batched cell copy of the gather step.
 //
-// A device receives the cells it owns itself by device copies into its [cell][cell buffer] staging images (mg.cpp, step 1).  With a
+// A device receives the cells it owns itself by device copies into its [cell][cell buffer] staging images (mg_contraction_exec.cpp stage_local; step 1 of mg.cpp's overview).  With a
 // block-cyclic distribution a device owns several cells of each tensor (contraction_multi_gpu.cu:154-193: 2 x 2 grids of cells over the
 // handle's devices), and hipMemcpyAsync costs the calling thread 2-3 us per cell — at eight handle devices the copies were the largest
 // part of the host time of a cutensorMgContraction call (tools/mg_host_cost_n.py).  One launch moves up to kMgCopyBatch cells: the

@@ -1,5 +1,5 @@
 // Index arithmetic of the block-cyclic redistribution (cutensorMgCopy): plain C++, included by the device code
-// (mg_redistribute.hip), by the host plan (mg.cpp) and, through ctamdMgCopyReplayOnHost, replayed by the CPU tests.
+// (mg_redistribute.hip), by the host plan (mg_copy.cpp) and, through ctamdMgCopyReplayOnHost, replayed by the CPU tests.
 //
 // A launch fills destination cells.  Every thread body below is written against (block index, thread index) arguments instead of
 // the HIP builtins, so the kernels are one-line wrappers and the host replay runs the SAME decomposition — which lane touches which

@@ -94,7 +94,7 @@ def replay_on_host(plan, alpha, A, B, beta, C, D, contract):
 
 def kboxes(extent, block_size, digits):
     """ctamdMgDescribeKBoxes -> list of {"wHi", "digits": [[lo, hi], ...]}: the boxes that tile the valid part of a ragged
-    contracted mode's padded index space (mg.cpp kbox_list)."""
+    contracted mode's padded index space (csrc/mg/mg_views.cpp kbox_list)."""
     import json
     buf = ctypes.create_string_buffer(1 << 14)
     f = (ctypes.c_int64 * max(len(digits), 1))(*digits)
@@ -104,18 +104,23 @@ def kboxes(extent, block_size, digits):
     return json.loads(buf.value.decode())
 
 
-def describe_plan(plan):
-    """ctamdMgDescribePlan -> dict: sharded / ordering mode labels, pieces in execution order, cell transfers."""
-    import json
+def describe_plan_raw(plan):
+    """ctamdMgDescribePlan -> the JSON text as the library wrote it."""
     n = 1 << 16
     while True:
         buf = ctypes.create_string_buffer(n)
         r = lib.ctamdMgDescribePlan(plan, buf, n)
         if r >= 0:
-            return json.loads(buf.value.decode())
+            return buf.value.decode()
         if r == -1:
             raise ValueError("ctamdMgDescribePlan: invalid arguments")
         n = -r + 16
+
+
+def describe_plan(plan):
+    """ctamdMgDescribePlan -> dict: sharded / ordering mode labels, pieces in execution order, local contractions, cell transfers."""
+    import json
+    return json.loads(describe_plan_raw(plan))
 
 
 class Contraction:

@@ -338,7 +338,7 @@ def test_every_extern_c_entry_point_is_a_function_try_block():
     (`) try {`, closed by a CTAMD_API_CATCH* handler) — a new entry point without one fails here, not in a caller's process."""
     csrc = os.path.join(ROOT, "cudalibrarysamples_amd", "csrc")
     missing, seen = [], 0
-    for rel in ("host/api.cpp", "host/blocksparse.cpp", "mg/mg.cpp", "mp/mp.cpp", "einsum/einsum_c.cpp"):
+    for rel in ("host/api.cpp", "host/blocksparse.cpp", "mg/mg.cpp", "mg/mg_diagnostics.cpp", "mg/mg_copy.cpp", "mp/mp.cpp", "einsum/einsum_c.cpp"):
         lines = open(os.path.join(csrc, rel)).read().split("\n")
         inside = False
         for i, line in enumerate(lines):

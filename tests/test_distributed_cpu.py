@@ -81,12 +81,12 @@ def _allgather_worker(rank, world, port, q):
 
     import oracle
     from cudalibrarysamples_amd import cutensormg as cm
-    from tests.test_mg_plan_cpu import free_mode_layout
+    from tests.mg_plan_cases import free_mode_layout
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    E = 64                                 # (shards of the free mode start at multiples of 16 indices: mg.cpp)
+    E = 64                                 # (shards of the free mode start at multiples of 16 indices: csrc/mg/mg_contraction_plan.cpp)
     rng = np.random.default_rng(7)         # the same full problem on every rank; a rank only TOUCHES its slabs until the gather
     A = rng.random((E, E), dtype=np.float32)       # A[i, k]
     B = rng.random((E, E), dtype=np.float32)       # B[k, j]
@@ -104,7 +104,7 @@ def _allgather_worker(rank, world, port, q):
     incoming = sorted((t["src"], t["cell"], t["bytes"]) for t in d["transfers"] if t["dst"] == rank and not t["local"])
     assert incoming == [(r, r, E * bj * 4) for r in range(world) if r != rank], incoming
     gathered = [torch.empty_like(b_slab) for _ in range(world)]
-    dist.all_gather(gathered, b_slab)                                   # RCCL ncclAllGather on the GPU box (mg.cpp), gloo here
+    dist.all_gather(gathered, b_slab)                                   # RCCL ncclAllGather on the GPU box (csrc/mg/mg_contraction_exec.cpp), gloo here
     c_slab = np.full((hi - lo, E), np.nan, dtype=np.float32)
     first_is_local = None
     for n, p in enumerate(mine):                                        # pieces in execution order: q coordinate ranges of B's grid

@@ -274,7 +274,7 @@ def test_mg_ragged_free_modes(mg, handle_devices):
 ])
 def test_mg_ragged_contracted_mode(mg, handle_devices, Ek, bs, dc):
     """A CONTRACTED mode whose extent is not a multiple of blockSize x deviceCount: the padding at the end of A's and B's cells
-    (NaN here) must not enter any sum.  The plan tiles the valid part of k's padded index space with boxes (mg.cpp kbox_list)
+    (NaN here) must not enter any sum.  The plan tiles the valid part of k's padded index space with boxes (csrc/mg/mg_views.cpp kbox_list)
     and the boxes accumulate into D; beta != 0 checks that only the first box applies it."""
     cm, torch = mg
     rng = np.random.default_rng(33)

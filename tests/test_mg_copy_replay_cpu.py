@@ -1,4 +1,4 @@
-"""The launches of cutensorMgCopy EXECUTED on the CPU: ctamdMgCopyReplayOnHost (csrc/mg/mg.cpp) walks a plan's launch tables over
+"""The launches of cutensorMgCopy EXECUTED on the CPU: ctamdMgCopyReplayOnHost (csrc/mg/mg_copy.cpp) walks a plan's launch tables over
 host cell buffers and runs every kernel thread by thread through the bodies of csrc/mg/mg_redistribute_layout.h — the same cells,
 forms, lane widths, runs and tiles the device executes — so a bug of the decomposition shows without a GPU.  Every case of
 tests/mg_copy_cases.py on plan-only handles with 1, 2, 4 and 8 distinct device ids, and 50 seeded random layouts, against the

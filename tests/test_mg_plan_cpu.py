@@ -8,21 +8,14 @@ import itertools
 import numpy as np
 import pytest
 
+from tests.mg_plan_cases import (_blog_post_shapes, free_mode_layout, ragged_contracted_layout, ragged_free_mode_layout,  # noqa: F401
+                                 sample_block_cyclic_layout)
+
 
 @pytest.fixture(scope="module")
 def cm(built):
     from cudalibrarysamples_amd import cutensormg
     return cutensormg
-
-
-def free_mode_layout(n, E):
-    """The layout bench.py uses for the cuTENSORMg case: C[i,j] = A[i,k] B[k,j] with the largest free mode i cut n ways
-    (A and C hold row slabs), B distributed along j (column slabs) — every device needs all of B: the all-gather."""
-    modes = ["ik", "kj", "ij"]
-    extent = dict(i=E, j=E, k=E)
-    block = [dict(i=E // n), dict(j=E // n), dict(i=E // n, j=E // n)]
-    dcount = [dict(i=n), dict(j=n), dict(i=n)]
-    return modes, extent, block, dcount
 
 
 def coverage(d, con, E):
@@ -118,11 +111,8 @@ def test_gather_in_waves_orders_cells_by_first_use(cm, n, waves, monkeypatch):
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
 def test_sample_block_cyclic_layout(cm, n):
     """contraction_multi_gpu.cu:154-217: 2 x 2 block-cyclic descriptors, cells owned by the handle devices cyclically."""
-    E, BS = 256, 64
-    modes = ["ik", "kj", "ij"]
-    block = [dict(i=BS, k=BS), dict(k=BS, j=BS), dict(i=BS, j=BS)]
-    dcount = [dict(i=2, k=2), dict(k=2, j=2), dict(i=2, j=2)]
-    with cm.Contraction(list(range(n)), modes, dict(i=E, j=E, k=E), block, dcount) as con:
+    E = 256
+    with cm.Contraction(list(range(n)), *sample_block_cyclic_layout(E, 64)) as con:
         d = con.describe()
         seen = check_transfers(d, con, n)
         assert (coverage(d, con, E) == 1).all()
@@ -188,16 +178,8 @@ def test_ragged_and_mixed_layouts_cover_c_once_and_gather_what_they_read(cm, see
     (the blog_post harness's ceil()-derived blocks): whatever p / q cut the planner takes, every element of C is produced exactly
     once (the p index ranges times the q-coordinate classes tile the padded index space), a cell is gathered at most once per
     consumer, and every cell a piece reads from a staging image was gathered to that device."""
-    rng = np.random.default_rng(100 + seed)
-    n = int(rng.choice([2, 3, 4]))
-    Ei, Ej, Ek = (int(rng.integers(40, 200)) for _ in range(3))
-    bi, bj = int(rng.integers(8, 48)), int(rng.integers(8, 48))
-    di = n
-    dj = int(rng.choice([1, 2])) if n % 2 == 0 else 1
-    modes = ["ik", "kj", "ij"]
-    extent = dict(i=Ei, j=Ej, k=Ek)
-    block = [dict(i=bi), dict(j=bj), dict(i=bi, j=bj)]
-    dcount = [dict(i=di), dict(j=dj), dict(i=di, j=dj)]
+    n, modes, extent, block, dcount = ragged_free_mode_layout(seed)
+    Ei, Ej, bi, bj, di, dj = extent["i"], extent["j"], block[2]["i"], block[2]["j"], dcount[2]["i"], dcount[2]["j"]
     with cm.Contraction(list(range(n)), modes, extent, block, dcount) as con:
         d = con.describe()
         check_transfers(d, con, n)
@@ -232,7 +214,7 @@ def test_ragged_and_mixed_layouts_cover_c_once_and_gather_what_they_read(cm, see
 
 @pytest.mark.parametrize("seed", range(8))
 def test_kboxes_tile_the_valid_index_space_exactly(cm, seed):
-    """Ragged CONTRACTED modes (mg.cpp kbox_list): idx = w + bs * b, b = sum digit_j * prod f_<j.  For random block sizes, digit
+    """Ragged CONTRACTED modes (csrc/mg/mg_views.cpp kbox_list): idx = w + bs * b, b = sum digit_j * prod f_<j.  For random block sizes, digit
     extents and extents, the boxes are disjoint, lie inside [0, extent) and cover it; at most digits + 1 of them."""
     rng = np.random.default_rng(500 + seed)
     for _ in range(40):
@@ -258,50 +240,14 @@ def test_kboxes_tile_the_valid_index_space_exactly(cm, seed):
 def test_ragged_contracted_mode_is_planned_as_boxes(cm):
     """k = 176 in blocks of 32 over 2 devices (5.5 blocks, padded to 6): {local block < 2} + {local block 2, grid digit 0}
     + the half block -> 3 local contractions per piece; a k that fills its padded space stays one box."""
-    modes = ["ik", "kj", "ij"]
-    block = [dict(i=32, k=32), dict(k=32, j=32), dict(i=32, j=32)]
-    dcount = [dict(i=2, k=2), dict(k=2, j=2), dict(i=2, j=2)]
-    with cm.Contraction([0, 1], modes, dict(i=128, j=128, k=176), block, dcount) as con:
+    with cm.Contraction([0, 1], *ragged_contracted_layout(176)) as con:
         assert con.describe()["numBoxes"] == 3
-    with cm.Contraction([0, 1], modes, dict(i=128, j=128, k=192), block, dcount) as con:
+    with cm.Contraction([0, 1], *ragged_contracted_layout(192)) as con:
         assert con.describe()["numBoxes"] == 1
     # 16-bit data: the boxes would accumulate through D with one rounding to the 16-bit type each -> still refused
     with pytest.raises(Exception) as ei:
-        cm.Contraction([0, 1], modes, dict(i=128, j=128, k=176), block, dcount, dtype=14)      # HIP_R_16BF
+        cm.Contraction([0, 1], *ragged_contracted_layout(176), dtype=14)      # HIP_R_16BF
     assert "NOT_SUPPORTED" in str(ei.value)
-
-
-def _blog_post_shapes(n, s):
-    """cuTENSORMg/blog_post.cu:155-175 (extents, ceil()-derived block sizes — including its N1 expression as written) and
-    :78-101 (device counts: from the last mode down, double while blocks and devices remain)."""
-    import math
-    M0, M1, M2, N0, N1, N2, K0, K1, K2 = "abcdefghi"
-    ext = {M0: 16, M1: 8 * s, M2: 8, N0: 16, N1: 8 * s, N2: 8, K0: 16, K1: 32, K2: 8}
-    nM = n // 2 if n >= 4 else n
-    nN = n // nM
-    M = ext[M0] * ext[M1] * ext[M2]
-    N = ext[N0] * ext[N1] * ext[N2]
-    bs = {M0: 16, M2: 8, N0: 16, N2: 8, K0: 16, K1: 16, K2: 8}
-    bs[M1] = math.ceil(math.ceil(M / math.ceil(M / 4096.0 / nM)) / nM / ext[M0] / ext[M2])
-    bs[N1] = math.ceil(math.ceil(N / math.ceil(N / 4096.0 / nN)) / nN / ext[N0] / ext[N1])
-    modes = [K0 + M0 + M1 + K1 + M2 + K2, K0 + N0 + K1 + N1 + K2 + N2, M0 + N0 + M1 + N1 + M2 + N2]
-    block, dcount = [], []
-    for m in modes:
-        dc = {c: 1 for c in m}
-        rem, changed = n, True
-        while changed:
-            changed = False
-            for c in reversed(m):
-                if rem <= 1:
-                    break
-                if dc[c] < ext[c] // bs[c]:
-                    dc[c] *= 2
-                    rem //= 2
-                    changed = True
-        assert rem == 1 or n == 1 or all(dc[c] >= ext[c] // bs[c] for c in m)
-        block.append({c: bs[c] for c in m})
-        dcount.append(dc)
-    return modes, ext, block, dcount
 
 
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
@@ -377,10 +323,7 @@ def test_all_gather_transport_is_selected_for_the_free_mode_layout(cm, n, monkey
         assert con.describe()["transport"] == "allgather"
     monkeypatch.delenv("CUTENSORMG_AMD_TRANSPORT")
     # the sample's 2 x 2 block-cyclic layout on 4 devices: cells are gathered, but not as one slab per device -> send/recv
-    modes = ["ik", "kj", "ij"]
-    blk = [dict(i=64, k=64), dict(k=64, j=64), dict(i=64, j=64)]
-    dc = [dict(i=2, k=2), dict(k=2, j=2), dict(i=2, j=2)]
-    with cm.Contraction([0, 1, 2, 3], modes, dict(i=256, j=256, k=256), blk, dc) as con:
+    with cm.Contraction([0, 1, 2, 3], *sample_block_cyclic_layout(256, 64)) as con:
         d = con.describe()
         assert d["transport"] == "sendrecv" or d["allGatherEligible"] != [0, 0]
         # remote scatter: some device stores pieces of C into cells another device owns -> that owner's stream must wait

@@ -1,5 +1,5 @@
 """The N > 1 cuTENSORMg data path EXECUTED on the CPU (no multi-GPU box is reachable from the build container): a plan built on a
-plan-only handle for 2 / 4 / 8 distinct device ids is walked by ctamdMgReplayOnHost (csrc/mg/mg.cpp) over host cell buffers —
+plan-only handle for 2 / 4 / 8 distinct device ids is walked by ctamdMgReplayOnHost (csrc/mg/mg_diagnostics.cpp) over host cell buffers —
 every transfer of the plan is a memcpy into a NaN-filled staging image of the receiving device, every local contraction runs
 through the CPU oracle on exactly the strided views / offsets / scalars / C-D aliasing that cutensorMgContraction hands to
 cutensorContract, staged pieces of C are scattered to their owners' cells — and the cells of D are compared with the dense
@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.test_mg_plan_cpu import _blog_post_shapes, free_mode_layout
+from tests.mg_plan_cases import _blog_post_shapes, free_mode_layout, ragged_block_cyclic_layout, sample_block_cyclic_layout
 
 
 @pytest.fixture(scope="module")
@@ -153,28 +153,15 @@ def test_gather_in_waves_executes(cm, n, waves, monkeypatch):
 def test_sample_block_cyclic_layout_executes(cm, n, beta):
     """contraction_multi_gpu.cu:154-217: 2 x 2 block-cyclic descriptors, cells owned by the handle devices cyclically (on 8 handle
     devices only four hold cells; the others still compute a shard and store into the owners' cells — the remote scatter)."""
-    E, BS = 96, 16
-    modes = ["ik", "kj", "ij"]
-    block = [dict(i=BS, k=BS), dict(k=BS, j=BS), dict(i=BS, j=BS)]
-    dcount = [dict(i=2, k=2), dict(k=2, j=2), dict(i=2, j=2)]
-    run_case(cm, n, modes, dict(i=E, j=E, k=E), block, dcount, beta=beta, seed=20 + n)
+    run_case(cm, n, *sample_block_cyclic_layout(96, 16), beta=beta, seed=20 + n)
 
 
 @pytest.mark.parametrize("seed", range(6))
 def test_ragged_block_cyclic_layouts_execute(cm, seed):
     """Extents that do not divide blockSize x deviceCount (blog_post.cu's ceil()-derived blocks) in free AND contracted modes: the
     cells' padding is NaN on the way in (a sum that touched it would be NaN) and must still be NaN on the way out."""
-    rng = np.random.default_rng(300 + seed)
-    n = int(rng.choice([2, 3, 4]))
-    Ei, Ej, Ek = (int(rng.integers(20, 70)) for _ in range(3))
-    bi, bj, bk = (int(rng.integers(4, 20)) for _ in range(3))
-    di = n
-    dj = int(rng.choice([1, 2])) if n % 2 == 0 else 1
-    dk = int(rng.choice([1, 2]))
-    modes = ["ik", "kj", "ij"]
-    block = [dict(i=bi, k=bk), dict(k=bk, j=bj), dict(i=bi, j=bj)]
-    dcount = [dict(i=di, k=dk), dict(k=dk, j=dj), dict(i=di, j=dj)]
-    d, padding = run_case(cm, n, modes, dict(i=Ei, j=Ej, k=Ek), block, dcount, beta=float(rng.choice([0.0, 1.5])), seed=seed)
+    n, modes, extent, block, dcount, beta = ragged_block_cyclic_layout(seed)
+    d, padding = run_case(cm, n, modes, extent, block, dcount, beta=beta, seed=seed)
     assert np.isnan(padding).all()
 
 

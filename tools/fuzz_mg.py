@@ -69,7 +69,7 @@ def main():
             geo[c] = (rnd.choice([8, 16, 24, 32]), rnd.choice([1, 1, 2]), rnd.choice([1, 1, 2, 3]))   # block, grid, local blocks
         ext = {c: geo[c][0] * geo[c][1] * geo[c][2] for c in geo}          # padded index space: whole blocks per cell
         # ragged extents (a third of the modes, contracted ones included): the last block is cut short; the padding of A and B
-        # holds NaN, which must never reach a valid output (blog_post.cu:168-175 ceil()-derived block sizes; mg.cpp kbox_list)
+        # holds NaN, which must never reach a valid output (blog_post.cu:168-175 ceil()-derived block sizes; csrc/mg/mg_views.cpp kbox_list)
         valid = {c: (ext[c] - rnd.randint(1, geo[c][0] - 1)) if (args.ragged and rnd.random() < 0.34) else ext[c] for c in geo}
         mA, mB, mC = M + K, N + K, M + N
         for m in (mA, mB, mC):
