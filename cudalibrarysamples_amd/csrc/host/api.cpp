@@ -330,7 +330,7 @@ cutensorStatus_t cutensorCreateTensorDescriptor(const cutensorHandle_t handle, c
     if (!supported_dtype(dataType)) return CUTENSOR_STATUS_NOT_SUPPORTED;
     const size_t es = dtype_size(dataType);
     if (alignmentRequirement == 0 || alignmentRequirement % es != 0) return CUTENSOR_STATUS_INVALID_VALUE;
-    cutensorTensorDescriptor* d = new (std::nothrow) cutensorTensorDescriptor();
+    std::unique_ptr<cutensorTensorDescriptor> d(new (std::nothrow) cutensorTensorDescriptor());   // owned here until it is filled
     if (d == nullptr) return CUTENSOR_STATUS_ALLOC_FAILED;
     d->numModes = numModes;
     d->dtype = dataType;
@@ -339,16 +339,16 @@ cutensorStatus_t cutensorCreateTensorDescriptor(const cutensorHandle_t handle, c
     d->stride.resize(numModes);
     int64_t run = 1;
     for (uint32_t i = 0; i < numModes; ++i) {
-        if (extent[i] <= 0) { delete d; return CUTENSOR_STATUS_INVALID_VALUE; }
+        if (extent[i] <= 0) return CUTENSOR_STATUS_INVALID_VALUE;
         if (stride != nullptr) {
-            if (stride[i] <= 0) { delete d; return CUTENSOR_STATUS_INVALID_VALUE; }
+            if (stride[i] <= 0) return CUTENSOR_STATUS_INVALID_VALUE;
             d->stride[i] = stride[i];
         } else {
             d->stride[i] = run;   // packed generalized column-major (blocksparse.cu:80-81)
             run *= extent[i];
         }
     }
-    *desc = d;
+    *desc = d.release();
     return CUTENSOR_STATUS_SUCCESS;
 } CTAMD_API_CATCH
 

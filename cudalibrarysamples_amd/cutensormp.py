@@ -53,11 +53,16 @@ check = ct.check
 i64, i32 = ct.i64, ct.i32
 
 
-def describe_plan(plan):
+def describe_plan_raw(plan):
+    """ctamdMpDescribePlan's text as the library wrote it"""
     n = lib.ctamdMpDescribePlan(plan, None, 0)
     buf = ctypes.create_string_buffer(n)
     lib.ctamdMpDescribePlan(plan, buf, n)
-    return json.loads(buf.value.decode())
+    return buf.value.decode()
+
+
+def describe_plan(plan):
+    return json.loads(describe_plan_raw(plan))
 
 
 class LocalWorld:

@@ -321,16 +321,22 @@ def test_allocation_failure_inside_an_entry_point_becomes_a_status(built, tmp_pa
     """No exception crosses the C ABI (csrc/host/api_guard.hpp): tests/harness/alloc_fail_harness.cpp replaces operator new, lets the
     k-th allocation of the contraction.cu:123-235 call sequence (and of the contraction_multi_gpu.cu:151-250 planning sequence on two
     device ids) throw std::bad_alloc for every k, and every entry point must answer CUTENSOR_STATUS_ALLOC_FAILED — an exception
-    that unwound into the harness's C-style frames would end the process in std::terminate."""
+    that unwound into the harness's C-style frames would end the process in std::terminate.  The same for the cuTENSORMp planning
+    sequence on one rank of a four-rank local world, under a gather and a reduce layout.  The harness also counts live allocations:
+    no round of the cuTENSORMp sweeps and of the single-GPU tensor-descriptor calls may leave an object behind (the plan, descriptors
+    and copies are owned from the moment they exist); cuTENSORMg's count is printed, not asserted."""
     import subprocess
     exe = str(tmp_path / "alloc_fail_harness")
     lib = os.path.join(ROOT, "cudalibrarysamples_amd", "lib")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
                            os.path.join(ROOT, "tests", "harness", "alloc_fail_harness.cpp"), "-o", exe,
-                           "-L", lib, "-lcutensorMg", "-lcutensor", "-Wl,-rpath," + lib])
+                           "-L", lib, "-lcutensorMp", "-lcutensorMg", "-lcutensor", "-Wl,-rpath," + lib])
     r = subprocess.run([exe, "mg"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "cutensor: alloc guard ok" in r.stdout and "cutensorMg: alloc guard ok" in r.stdout, r.stdout
+    assert "cutensorMp: alloc guard ok" in r.stdout, r.stdout
+    for sweep in ("cutensorMp gather", "cutensorMp reduce", "cutensor descriptors"):
+        assert "%s: alloc guard ok" % sweep in r.stdout and "%s: 0 rounds left allocations behind" % sweep in r.stdout, r.stdout
 
 
 def test_every_extern_c_entry_point_is_a_function_try_block():
@@ -338,7 +344,7 @@ def test_every_extern_c_entry_point_is_a_function_try_block():
     (`) try {`, closed by a CTAMD_API_CATCH* handler) — a new entry point without one fails here, not in a caller's process."""
     csrc = os.path.join(ROOT, "cudalibrarysamples_amd", "csrc")
     missing, seen = [], 0
-    for rel in ("host/api.cpp", "host/blocksparse.cpp", "mg/mg.cpp", "mg/mg_diagnostics.cpp", "mg/mg_copy.cpp", "mp/mp.cpp", "einsum/einsum_c.cpp"):
+    for rel in ("host/api.cpp", "host/blocksparse.cpp", "mg/mg.cpp", "mg/mg_diagnostics.cpp", "mg/mg_copy.cpp", "mp/mp.cpp", "mp/mp_describe.cpp", "einsum/einsum_c.cpp"):
         lines = open(os.path.join(csrc, rel)).read().split("\n")
         inside = False
         for i, line in enumerate(lines):

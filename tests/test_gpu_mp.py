@@ -10,9 +10,15 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests import mp_plan_cases as pc
+from tests.mp_plan_cases import GPU_CASES as CASES
+from tests.mp_plan_cases import GPU_REDUCE_CASES as REDUCE_CASES
 from util import to_device
 
 pytestmark = pytest.mark.gpu
+
+GUARD = 4096            # bytes behind the workspace a plan asks for; no call may touch them
+GUARD_BYTE = 0xA5
 
 
 @pytest.fixture(scope="module")
@@ -24,23 +30,25 @@ def mp(built):
     return cutensormp, ct, torch
 
 
-def cell_slices(extent, p, cell):
-    """Index ranges of grid cell `cell` (first mode fastest) for block size ceil(extent / p)
+def cell_slices(extent, p, cell, bs=None):
+    """Index ranges of grid cell `cell` (first mode fastest) for block sizes `bs`, by default ceil(extent / p)
     (cutensorMp_contraction.cu:143-153)."""
     out = []
-    for e, n in zip(extent, p):
-        bs = -(-e // n)
+    for i, (e, n) in enumerate(zip(extent, p)):
+        b = bs[i] if bs else -(-e // n)
         c = cell % n
         cell //= n
-        out.append(slice(min(e, c * bs), min(e, (c + 1) * bs)))
+        out.append(slice(min(e, c * b), min(e, (c + 1) * b)))
     return tuple(out)
 
 
-def local_block(G, p, cell):
-    """The rank's local buffer: block extents ceil(E/p), packed first-mode-fastest, the valid part filled."""
-    bs = [-(-e // n) for e, n in zip(G.shape, p)]
+def local_block(G, p, cell, bs=None, pad=0):
+    """The rank's local buffer: block extents `bs` (by default ceil(E/p)), first-mode-fastest, the first mode's block padded by `pad`
+    elements (the element strides of mp_plan_cases.element_strides), the valid part filled."""
+    bs = list(bs) if bs else [-(-e // n) for e, n in zip(G.shape, p)]
+    bs[0] += pad
     buf = np.zeros(bs, dtype=G.dtype, order="F")
-    sl = cell_slices(G.shape, p, cell)
+    sl = cell_slices(G.shape, p, cell, [b - (pad if i == 0 else 0) for i, b in enumerate(bs)])
     sub = G[sl]
     buf[tuple(slice(0, s) for s in sub.shape)] = sub
     return buf
@@ -57,9 +65,11 @@ def np_dtype_info(name):
     }[name]
 
 
-def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=None, seed=0):
+def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=None, seed=0, pad=0, block=None):
     """eq 'ab,bc->ac' (first listed mode is the fastest, as in the sample :191-227); ext {label: extent};
-    dist = three dicts {label: ranks along that mode} for A, B, C; ranks = optional cell->rank permutations."""
+    dist = three dicts {label: ranks along that mode} for A, B, C; ranks = optional cell->rank permutations; pad = elements the first
+    mode's block is padded by in the element strides of A, B and C (0: packed); block = {label: block size} where it is not
+    ceil(extent / ranks).  The workspace is the required size plus GUARD bytes of a pattern no call may touch."""
     cmp, ct, torch = mp
     npdt, ctdt, compute, tol, tdt = np_dtype_info(dtype)
     lhs, mc = eq.split("->")
@@ -79,6 +89,7 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
 
     G = [rand(m) for m in modes]
     P = [[dist[k].get(l, 1) for l in modes[k]] for k in range(3)]
+    BS = [pc.block_sizes(ext, modes[k], P[k], block) for k in range(3)]
     perm = ranks or [None, None, None]
     ref = alpha * np.einsum("%s,%s->%s" % (ma, mb, mc), G[0].astype(np.complex128 if "c" in dtype else np.float64),
                             G[1].astype(np.complex128 if "c" in dtype else np.float64)) + beta * G[2]
@@ -92,6 +103,7 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
     world = cmp.LocalWorld(nranks)
     results = [None] * nranks
     described = [None] * nranks
+    guards = [None] * nranks
 
     def body(r):
         torch.cuda.set_device(0)
@@ -103,9 +115,10 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
             d = ctypes.c_void_p()
             pr = None if perm[k] is None or int(np.prod(P[k])) == 1 else ct.i32(perm[k])
             cmp.check(cmp.cutensorMpCreateTensorDescriptor(h, ctypes.byref(d), len(modes[k]), ct.i64([ext[l] for l in modes[k]]),
-                                                           None, None, None, ct.i64(P[k]), nranks, pr, ctdt))
+                                                           ct.i64(pc.element_strides(BS[k], pad)) if pad else None, ct.i64(BS[k]) if block else None,
+                                                           None, ct.i64(P[k]), nranks, pr, ctdt))
             descs.append(d)
-            blk = local_block(G[k], P[k], cell_of(k, r))
+            blk = local_block(G[k], P[k], cell_of(k, r), BS[k], pad)
             if tdt is not None:
                 t = torch.from_numpy(np.ascontiguousarray(blk.ravel(order="K"))).to(tdt).cuda()
             else:
@@ -122,7 +135,7 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
         need = ctypes.c_uint64(0)
         cmp.check(cmp.cutensorMpPlanGetAttribute(h, plan, cmp.PLAN_REQUIRED_WORKSPACE_DEVICE, ctypes.byref(need), 8))
         described[r] = cmp.describe_plan(plan)
-        ws = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device="cuda")
+        ws = torch.full((int(need.value) + GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
         if "c" in dtype:
             a, b = (ctypes.c_float * 2)(alpha, 0.0), (ctypes.c_float * 2)(beta, 0.0)
         elif dtype == "f64":
@@ -138,6 +151,7 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
             cmp.check(cmp.cutensorMpContract(h, plan, ctypes.byref(a), bufs[0][0].data_ptr(), bufs[1][0].data_ptr(), ctypes.byref(b),
                                              bufs[2][0].data_ptr(), bufs[2][0].data_ptr(), ws.data_ptr(), None))
             stream.synchronize()
+        guards[r] = bool((ws[int(need.value):] == GUARD_BYTE).all().item())
         out = bufs[2][0].to(torch.float32).cpu().numpy() if tdt is not None else bufs[2][0].cpu().numpy()
         results[r] = np.reshape(out, bufs[2][1].shape, order="F")
         cmp.check(cmp.cutensorMpDestroyPlan(plan))
@@ -154,7 +168,8 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
 
     scale = max(1.0, float(np.max(np.abs(ref))))
     for r in range(nranks):
-        sl = cell_slices(ref.shape, P[2], cell_of(2, r))
+        assert guards[r], "rank %d wrote behind the %d bytes of workspace its plan asked for (plan %s)" % (r, described[r]["requiredDevice"], described[r])
+        sl = cell_slices(ref.shape, P[2], cell_of(2, r), BS[2])
         want = ref[sl]
         got = results[r][tuple(slice(0, s) for s in want.shape)]
         err = float(np.max(np.abs(got - want))) if want.size else 0.0
@@ -163,39 +178,11 @@ def run_case(mp, eq, ext, dist, nranks, dtype="f32", alpha=1.0, beta=0.0, ranks=
     return described
 
 
-CASES = [
-    # name, eq, extents, (distA, distB, distC), nranks, dtype, alpha, beta
-    ("row-sharded, B replicated: no exchange", "mk,kn->mn", dict(m=96, k=80, n=64), ({"m": 2}, {}, {"m": 2}), 2, "f32", 1.0, 0.0),
-    ("2x2 grids, ragged blocks", "mk,kn->mn", dict(m=100, k=72, n=52), ({"m": 2, "k": 2}, {"k": 2, "n": 2}, {"m": 2, "n": 2}), 4, "f32", 1.1, 0.0),
-    ("k distributed, C replicated", "mk,kn->mn", dict(m=48, k=128, n=40), ({"k": 4}, {"k": 4}, {}), 4, "f32", 1.0, 0.0),
-    ("k distributed, C sharded, beta", "mk,kn->mn", dict(m=64, k=96, n=48), ({"k": 2}, {"k": 2}, {"n": 2}), 2, "f32", 0.7, 0.5),
-    ("three ranks, multi-mode", "akcl,lbk->abc", dict(a=30, b=21, c=9, k=16, l=12), ({"c": 3}, {"b": 3}, {"a": 3}), 3, "f32", 1.0, 0.5),
-    ("sub-box transfers", "mk,kn->mn", dict(m=64, k=64, n=64), ({"k": 4}, {"n": 4}, {"m": 2, "n": 2}), 4, "f32", 1.0, 0.0),
-    ("fp64", "mk,kn->mn", dict(m=40, k=56, n=24), ({"m": 2}, {"n": 2}, {"m": 2}), 2, "f64", 1.0, 0.25),
-    ("bf16", "mk,kn->mn", dict(m=128, k=256, n=128), ({"k": 2}, {"n": 2}, {"m": 2}), 2, "bf16", 1.0, 0.0),
-    ("more ranks than blocks along a mode", "mk,kn->mn", dict(m=5, k=16, n=8), ({"m": 4}, {}, {"m": 4}), 4, "f32", 1.0, 0.0),
-]
-
-
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_mp_contraction_over_local_world(mp, case):
     _, eq, ext, dist, nranks, dtype, alpha, beta = case
     run_case(mp, eq, ext, dist, nranks, dtype, alpha, beta)
-
-
-REDUCE_CASES = [
-    # name, eq, extents, (distA, distB, distC), nranks, dtype, alpha, beta
-    ("C replicated: all-reduce in the user's D", "mk,kn->mn", dict(m=48, k=128, n=40), ({"k": 4}, {"k": 4}, {}), 4, "f32", 1.0, 0.5),
-    ("C cut along its last mode: slots are slabs", "mk,kn->mn", dict(m=64, k=96, n=48), ({"k": 2}, {"k": 2}, {"n": 2}), 2, "f32", 0.7, 0.5),
-    ("C cut along its first mode: packed slots", "mk,kn->mn", dict(m=64, k=96, n=48), ({"k": 2}, {"k": 2}, {"m": 2}), 2, "f32", 1.0, 0.0),
-    ("ragged 2x2 grid of C, two contracted modes cut", "mkl,lkn->mn", dict(m=50, k=12, l=10, n=27), ({"k": 2, "l": 2}, {"l": 2, "k": 2}, {"m": 2, "n": 2}), 4, "f32", 1.0, 0.25,
-     [None, [0, 2, 1, 3], None]),   # B's grid is (l, k): this rank order gives every rank the same (k, l) block of A and B
-    ("the headline einsum, shrunk, K cut over four ranks", "dcba,ebcd->ea", dict(a=24, b=16, c=8, d=16, e=24), ({"b": 4}, {"b": 4}, {}), 4, "f32", 1.0, 0.0),
-    ("complex", "mk,kn->mn", dict(m=20, k=64, n=12), ({"k": 2}, {"k": 2}, {"n": 2}), 2, "c64", 1.0, 0.5),
-    ("bf16", "mk,kn->mn", dict(m=128, k=512, n=64), ({"k": 2}, {"k": 2}, {}), 2, "bf16", 1.0, 0.0),
-    ("fp64, three ranks, one with an empty block of C", "mk,kn->mn", dict(m=4, k=90, n=16), ({"k": 3}, {"k": 3}, {"m": 3}), 3, "f64", 1.0, 0.5),
-]
 
 
 @pytest.mark.timeout(300)
@@ -210,6 +197,42 @@ def test_mp_contracted_mode_distributed_both_algorithms(mp, monkeypatch, case, a
     assert all(x["algorithm"] == algo for x in d), d[0]
     if algo == "reduce":
         assert all(x["sends"] == [] and x["recvs"] == [] for x in d)        # no operand leaves its rank
+
+
+PADDED_REDUCE = [("C replicated", pc.PADDED_REDUCE_REPLICATED), ("C cut along n", pc.PADDED_REDUCE_CUT_N)]
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("algo", ["reduce", "gather"])
+@pytest.mark.parametrize("case", PADDED_REDUCE, ids=[c[0] for c in PADDED_REDUCE])
+def test_mp_padded_element_strides_both_algorithms(mp, monkeypatch, case, algo):
+    """Element strides that are not the packed layout of the block (first mode's block + 3): under reduce the partial is staged and copied
+    in and out (replicated C) or the received slot is unpacked into the padded block (C cut along n); under gather nothing is sent
+    straight from a block."""
+    eq, ext, dist, nranks = case[1]
+    monkeypatch.setenv("CUTENSORMP_AMD_ALGO", algo)
+    d = run_case(mp, eq, ext, dist, nranks, "f32", 0.7, 0.5, pad=pc.PAD)
+    assert all(x["algorithm"] == algo for x in d), d[0]
+    assert not any(x["reduceDirect"] or x["recvDirect"] for x in d) and not any(t["direct"] for x in d for t in x["sends"])
+
+
+@pytest.mark.timeout(300)
+def test_mp_padded_element_strides_gather(mp):
+    """A cut along k, B along n, C along m, every block padded: packed sub-box sends, staged operands, D written at padded strides."""
+    eq, ext, dist, nranks = pc.PADDED_GATHER
+    d = run_case(mp, eq, ext, dist, nranks, "f32", 1.0, 0.5, pad=pc.PAD)
+    assert all(x["algorithm"] == "gather" and x["sends"] and not any(t["direct"] for t in x["sends"]) for x in d), d[0]
+
+
+@pytest.mark.timeout(300)
+def test_mp_copy_of_more_than_one_launch(mp):
+    """mp_plan_cases.PEELED: blocks declared larger than the extent in seven modes — the pack of the half of A a rank sends and the local
+    copy of the half it keeps have more unfusable modes than one element-wise launch takes, and run as a host loop of launches."""
+    eq, ext, dist, nranks = pc.PEELED
+    d = run_case(mp, eq, ext, dist, nranks, "f32", 1.0, 0.0, block=pc.PEELED_BLOCK)
+    for x in d:
+        assert [len(t["pack"]["launches"]) for t in x["sends"]] == [8]
+        assert [len(c["launches"]) for c in x["operands"][0]["localCopies"]] == [8]
 
 
 @pytest.mark.timeout(300)
