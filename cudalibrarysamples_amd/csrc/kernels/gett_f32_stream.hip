@@ -27,7 +27,8 @@
 //     the MFMAs that are still to be issued.  The ring walk is unrolled S times: every LDS address is
 //     a lane-constant base plus an immediate.
 //   * split-K partial tiles are written in the accumulator's own register order (16 B per lane,
-//     1 KiB per wave-instruction) and folded by splitk_reduce_frag_kernel.
+//     1 KiB per wave-instruction) and folded by splitk_reduce_frag_kernel.  The flat entries issue their last K-tile accumulator by
+//     accumulator and store each finished group under the MFMAs of the next (gett_f32_stream_kloop.inc).
 //
 // Roofline: fp32 MFMA (v_mfma_f32_16x16x4_f32, 256 flop/clk/CU); algorithmic flops = 2*L*M*N*K,
 // algorithmic bytes = |A| + |B| + |D|.
@@ -49,6 +50,11 @@ constexpr int kStreamBK = 32;
 // (gett_f32_stream_kloop.inc), to price the straight-line tail on its own
 #ifndef CTAMD_FLAT_STRAIGHT_TAIL
 #define CTAMD_FLAT_STRAIGHT_TAIL 1
+#endif
+// measurement: -DCTAMD_FLAT_EARLY_PARTIALS=0 builds the flat entries with the kk-major last K-tile and the partial stores behind it,
+// to price the fragment-ordered last tile (CTAMD_TILE_LAST_EARLY in gett_f32_stream_kloop.inc) on its own
+#ifndef CTAMD_FLAT_EARLY_PARTIALS
+#define CTAMD_FLAT_EARLY_PARTIALS 1
 #endif
 
 // 64 lanes x 16 B into one contiguous 1-KiB piece of LDS starting at the wave-uniform address dst (the
@@ -767,16 +773,25 @@ __device__ __forceinline__ void gett_f32_stream_flat_body(const StreamFlatParams
 #include "gett_f32_stream_ring.inc"
     }
 
-#include "gett_f32_stream_kloop.inc"
-
     // accumulator-order partials, one tile image per slice: [slice][wave][i][j][lane] x 16 B, write-through as in the general entry
+    auto partials_rsrc = [&]() -> BufRsrc {
+        f32x4* P = reinterpret_cast<f32x4*>(p.partial) + ((size_t)slice * 4 + wave) * (size_t)(TM * TN * 64);
+        return make_rsrc(reinterpret_cast<const float*>(P));
+    };
+#if CTAMD_FLAT_STRAIGHT_TAIL && CTAMD_FLAT_EARLY_PARTIALS
+    // the last K-tile stores the image under its own MFMAs; stamp(4) is behind the last store
+#define CTAMD_KLOOP_EARLY_PARTIALS 1
+#include "gett_f32_stream_kloop.inc"
+#undef CTAMD_KLOOP_EARLY_PARTIALS
+#else
+#include "gett_f32_stream_kloop.inc"
     const int laneE = lane_now();
-    f32x4* P = reinterpret_cast<f32x4*>(p.partial) + ((size_t)slice * 4 + wave) * (size_t)(TM * TN * 64);
-    const BufRsrc rP = make_rsrc(reinterpret_cast<const float*>(P));
+    const BufRsrc rP = partials_rsrc();
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) store_wt_16(acc[i][j], rP, (uint32_t)(((i * TN + j) * 64 + laneE) * 16));
+#endif
     stamp(4);
     stamp(6);
 }

@@ -1,7 +1,8 @@
 // gett_f32_stream_kloop.inc — the multiplying waves of gett_f32_stream_kernel from their first barrier to the last MFMA, included by
 // both entries of the kernel (gett_f32_stream.hip), so that the K loop, its barriers and the LDS reads are one text.  Expects in
 // scope: Cfg, BM, BN, S, TM, TN, STAGE, OpA, OpB, lds, nTiles, wave, wave8, lane, tlog, lane_now(), stamp(slot); leaves the
-// accumulators in acc[TM][TN] and wm / wn (this wave's place in the 2 x 2 wave grid).
+// accumulators in acc[TM][TN] and wm / wn (this wave's place in the 2 x 2 wave grid).  Included with CTAMD_KLOOP_EARLY_PARTIALS 1 (the
+// flat entries; also expects partials_rsrc()), it stores acc as the slice's partial image as well: nothing is left to the includer.
     // =============================== multipliers ======================================================
     __builtin_amdgcn_s_setprio(2);
     const int wm = wave & 1, wn = wave >> 1;
@@ -85,6 +86,51 @@
         }                                                                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                 \
     }
+#if CTAMD_KLOOP_EARLY_PARTIALS
+    // The LAST K-tile of a flat entry (gett_f32_stream_flat_body defines CTAMD_KLOOP_EARLY_PARTIALS 1 and partials_rsrc()), issued by
+    // accumulator instead of kk-major, so that the split-K partials leave under its MFMAs and not in one burst behind them.  The
+    // fragments go in groups of two (the first group of three when TM x TN is odd); a group's 8 k-steps x its accumulators are issued
+    // k-step by k-step, alternating between the accumulators (no two consecutive MFMAs share one), and every accumulator receives
+    // 16-step 0 with kk 0..3, then 16-step 1 with kk 0..3 — the kk-major order's own chain, so the bits are the same.  A group that is
+    // final is stored under the NEXT group, one 1-KiB store behind each of its first k-steps: the store never waits for the MFMA whose
+    // result it reads, and the memory pipe of a multiplying wave, idle until here, takes the tile image while the matrix pipe is busy.
+    // Behind the last group only its own two stores remain.  The odd 16-step's fragments are fetched under the first group's MFMAs.
+    // Same addresses as the general entry's epilogue: [slice][wave][i][j][lane] x 16 B.
+#define CTAMD_TILE_LAST_EARLY(U)                                                                           \
+    {                                                                                                      \
+        constexpr int NF = TM * TN, G0 = 2 + (NF & 1), NG = (NF - G0) / 2 + 1;                             \
+        static_assert(NF >= 4, "at least two groups of fragments");                                        \
+        const uint32_t laneBytes = (uint32_t)lane_now() * 16u;                                             \
+        const BufRsrc rP = partials_rsrc();                                                                \
+        load1(lds + (U) * STAGE);                                                                          \
+        _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                   \
+            const int f0 = g == 0 ? 0 : G0 + 2 * (g - 1), nf = g == 0 ? G0 : 2;    /* this group */        \
+            const int pf0 = g <= 1 ? 0 : f0 - 2, pnf = g == 0 ? 0 : (g == 1 ? G0 : 2);   /* the one before */ \
+            _Pragma("unroll") for (int s = 0; s < 8; ++s) {                                                \
+                _Pragma("unroll") for (int c = 0; c < nf; ++c) {                                           \
+                    const int i = (f0 + c) / TN, j = (f0 + c) % TN, kk = s & 3;                            \
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(s < 4 ? a0[i][kk] : a1[i][kk],        \
+                                                                     s < 4 ? b0[j][kk] : b1[j][kk], acc[i][j], 0, 0, 0); \
+                }                                                                                          \
+                if (s < pnf) {                                                                             \
+                    __builtin_amdgcn_sched_barrier(0);                                                     \
+                    store_wt_16(acc[(pf0 + s) / TN][(pf0 + s) % TN], rP, (uint32_t)((pf0 + s) * 1024) + laneBytes); \
+                    __builtin_amdgcn_sched_barrier(0);                                                     \
+                }                                                                                          \
+            }                                                                                              \
+            if (g == 0) {    /* n x (1 MFMA, 2 LDS reads): the odd step's fragments are back before the group's fifth k-step */ \
+                _Pragma("unroll") for (int z = 0; z < (TM + 4 * TN + 1) / 2; ++z) {                        \
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                     \
+                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                     \
+                }                                                                                          \
+            }                                                                                              \
+            __builtin_amdgcn_sched_barrier(0);                                                             \
+        }                                                                                                  \
+        stamp(3);                                                                                          \
+        _Pragma("unroll") for (int f = NF - 2; f < NF; ++f)                                                \
+            store_wt_16(acc[f / TN][f % TN], rP, (uint32_t)(f * 1024) + laneBytes);                        \
+    }
+#endif
 #define CTAMD_BODY_MID(U) CTAMD_TILE_BODY(U, false)
     // compile-time unrolling over the ring slots
 #define CTAMD_FOR_SLOTS(M)                                                     \
@@ -97,6 +143,20 @@
     stamp(2);
     const int r = nTiles - t;
 #define CTAMD_BODY_END(U) CTAMD_TILE_BODY(U, (U) == S - 1)
+#if CTAMD_KLOOP_EARLY_PARTIALS
+    // the flat entries: the same three ends, the last tile fragment by fragment with the partials stored under it (stamp(3) is inside)
+    static_assert(Cfg::FLAT && S == 3, "the flat entries run the 3-deep ring");
+    if (r == S) {
+        CTAMD_TILE_BODY(0, false)
+        CTAMD_TILE_BODY(1, false)
+        CTAMD_TILE_LAST_EARLY(2)
+    } else if (r == 2) {
+        CTAMD_TILE_BODY(0, false)
+        CTAMD_TILE_LAST_EARLY(1)
+    } else {
+        CTAMD_TILE_LAST_EARLY(0)
+    }
+#else
     if (r == S) {          // the common case (whole ring turns): straight-line code, no per-tile branch
         CTAMD_FOR_SLOTS(CTAMD_BODY_END)
     } else if constexpr (Cfg::FLAT && CTAMD_FLAT_STRAIGHT_TAIL) {
@@ -135,6 +195,7 @@
         CTAMD_TILE_BODY_AT2(lds + u * STAGE, lds, true, load0t, load1t)     // u == r - 1
     }
     stamp(3);
+#endif
     if constexpr (Cfg::ABL == 3) {
         if (tlog != nullptr && wave8 == 0 && lane_now() == 0) tlog[8] = waitC;
     }
