@@ -24,7 +24,7 @@
 
 using namespace ctamd;
 
-extern "C" int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len);   // api.cpp
+extern "C" int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len);   // describe.cpp
 
 struct cutensorBlockSparseTensorDescriptor {
     uint32_t numModes = 0;

@@ -1,5 +1,5 @@
 // contraction_route.cpp — how a contraction runs: reduce lone modes first, peel, mode-table kernel, ranked tiled candidates, repack,
-// a tiled family or the simple kernel.  The plan builders (api.cpp) and cutensorEstimateWorkspaceSize take their decisions from here.
+// a tiled family or the simple kernel.  The plan builders (create_plan.cpp) and cutensorEstimateWorkspaceSize take their decisions from here.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -410,7 +410,7 @@ static void peel_fix_alignment(cutensorOperationDescriptor& inner, const std::ve
 }
 
 // ---- the routes of a contraction, in the order they are tried -------------------------------------------------------------------
-// The plan builders (api.cpp, build_contraction) and the workspace estimate (estimate_contraction below) walk the same functions on
+// The plan builders (create_plan.cpp, build_contraction) and the workspace estimate (estimate_contraction below) walk the same functions on
 // the same PlanRequest: the operands reduced over their lone modes first (split_lone_modes), then the view, then route_peeled,
 // route_mode_table, rank_tiled_candidates, route_repack, and what is left is a tiled plan or the simple kernel (route_tiled).  Every
 // condition on the way, and every test-hook switch that moves a problem from one route to another, is read here and nowhere else.

@@ -14,6 +14,7 @@
 #include <cutensor.h>
 
 #include "api_guard.hpp"
+#include "plan_store.hpp"
 
 // Every behaviour-changing environment switch of this library is read through CTAMD_HOOK_ENV (api_guard.hpp): live in the test-hooks
 // flavour (lib_hooks/), a null pointer in the production library.  That covers the switches the test-suite drives behaviour with
@@ -313,51 +314,12 @@ struct cutensorPlan {
     ctamd::ReducePlan red;
 };
 
-struct PlanCacheEntry {
-    std::string key;
-    int         kernel;
-    uint32_t    splitK;
-};
-
-// Plan memo: the einsum.cu flow creates descriptors and a plan inside every call (einsum.cu:264-329) with the plan cache on
-// (:443-445), so a repeated problem must cost a lookup, not a planning pass.  The key is a fixed-size POD built straight from
-// the operation descriptor + preference + workspace limit (no strings, no allocation); the value is a finished prototype plan
-// that a hit clones.  Problems with more than kMaxModes mode slots in total are simply not memoised.
-struct PlanMemoKey {
-    static constexpr int kMaxModes = 40;          // sum of the mode counts of A, B, C, D
-    uint64_t wsLimit = 0;
-    int32_t  algo = 0, kernelRank = 0, autotune = 0, incrementalCount = 0;
-    uint32_t alignment[4] = {0, 0, 0, 0};
-    uint8_t  kind = 0, dtype = 0, compute = 0, scalarType = 0;
-    uint8_t  n[4] = {0, 0, 0, 0};
-    uint8_t  op[4] = {0, 0, 0, 0};                 // opA, opB, opC, opReduce
-    uint8_t  present = 0, operandsStreamed = 0, dtypeD = 0, dtypeC = 0;   // (dtype above is A's; C's is 255 when there is no C)
-    uint32_t used = 0;                             // int64 words of data[] in use
-    uint32_t dtypeB = 0;                           // B's type + 1 where it differs from A's (mixed contractions), else 0
-                                                   // (no implicit padding anywhere in the head: it is hashed and compared bytewise)
-    int64_t  data[3 * kMaxModes];                  // per tensor: modes, extents, strides
-    uint64_t hash() const;
-    bool operator==(const PlanMemoKey& o) const;
-};
-struct PlanMemoEntry {
-    PlanMemoKey key;
-    std::shared_ptr<const cutensorPlan> proto;
-    uint64_t stamp = 0;                            // last use, for LRU eviction
-};
-
 struct cutensorHandle {
     int device = 0;
     bool haveDevice = false;            // a GPU was visible at cutensorCreate (false: descriptors and plans only)
     int numCUs = 256;
-    int clockKHz = 2400000;
-    std::mutex mtx;
-    uint32_t planCacheCapacity = 64;    // a fresh handle can read a plan-cache file before any resize (contraction_plan_cache.cu:132-152)
-    std::map<std::string, PlanCacheEntry> planCache;   // problem signature -> tuned choice (what the cache FILE holds)
-    std::unordered_map<uint64_t, PlanMemoEntry> planMemo;   // hashed POD key -> finished prototype plan (at most planCacheCapacity)
-    uint64_t memoClock = 0;
-    std::atomic<uint64_t> memoHits{0}, memoMisses{0};
-    std::atomic<int> pendingCount{0};                  // == pending.size(), readable without the lock
-    int logLevel = 0;
+    std::mutex mtx;                     // syncPool / syncNext, xcdSpeed, and the late upload of a plan's mode table (mode_table_on_device)
+    ctamd::PlanStore plans;             // plan cache, plan memo and incremental autotuning, behind a lock of their own (plan_store.hpp)
     // {arrivals, departures} counter pairs for in-launch split-K folds, 64 B apart, zeroed once; a launch
     // draws the next slot round-robin and its last workgroup re-arms it (gett_f32_stream.hip)
     // relative sustained shader clock of the 8 XCDs under the streaming GETT kernel (measured once per handle by
@@ -375,17 +337,6 @@ struct cutensorHandle {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
         std::mutex mtx;
     } prof;
-    // incremental autotuning (CUTENSOR_AUTOTUNE_MODE_INCREMENTAL, contraction_plan_cache.cu:215-237): per problem, the
-    // candidates tried so far with their measured time; the best one is what the plan cache holds
-    struct TuneState {
-        int      next = 0;                 // next candidate rank to try
-        int      bestKernel = -1;
-        uint32_t bestSplitK = 1;
-        float    bestMs = 1e30f;
-    };
-    std::map<std::string, TuneState> tuning;
-    struct PendingMeasurement { std::string key; int kernel; uint32_t splitK; hipEvent_t e0, e1; };
-    std::vector<PendingMeasurement> pending;   // cutensorContract calls of tuning plans whose events were not read yet
 };
 
 // ---- contraction routing (contraction_route.cpp) -----------------------------------------------------------------------------
@@ -458,5 +409,11 @@ TiledRoute rank_tiled_candidates(const PlanRequest& rq, const ContractionView& v
 bool route_repack(const PlanRequest& rq, const ContractionView& v, const TiledRoute& r, TwoStepSplit& rs);
 void route_tiled(const PlanRequest& rq, const ContractionView& v, TiledRoute& r);
 cutensorStatus_t estimate_contraction(const PlanRequest& rq, cutensorWorksizePreference_t workspacePref, uint64_t* estimate);
+
+// ---- the two helpers plan creation (create_plan.cpp) and execution (exec_contraction.cpp) share ---------------------------------
+// the fold that matches a kernel's split-K partials (exec_contraction.cpp; the measured selection of create_plan.cpp times it too)
+CTAMD_HIDDEN hipError_t launch_splitk_fold(int family, const GettKernelInfo& k, const SplitKReduceParams& r, hipStream_t stream);
+// the mode table of a plan in device memory; null: no memory, or no device (create_plan.cpp; exec_contraction.cpp uploads late)
+CTAMD_HIDDEN std::shared_ptr<const WideMode> upload_mode_table(const std::vector<WideMode>& tab);
 
 }  // namespace ctamd

@@ -713,7 +713,7 @@ bool pick_h16_choice(const ContractionView& v, uint64_t wsLimit, int numCUs, Con
         // operand ring (gett_h16p.hip, curOK): one M and one N mode, 16-byte lanes in D (batch modes stream since round 6).  Tiles that cannot stream are set up
         // serially behind the previous epilogue and the kernel is SLOWER than the one-tile kernel then (measured with beta != 0, the one
         // condition only the call knows: 8192^3 1377 against 1429-1435 TFLOP/s, 8192^2 x 1024 692 against 819, x 512 432 against 526,
-        // profiles/r05r_h16p_beta.jsonl — cutensorContract launches the one-tile twin for beta != 0, api.cpp).
+        // profiles/r05r_h16p_beta.jsonl — cutensorContract launches the one-tile twin for beta != 0, exec_contraction.cpp).
         // ... and the hand-over of tile i's last K-tile bodies to tile i + 1 needs an even K-tile count (gett_h16p.hip, switchAt; two
         // K-tiles per tile stream since round 6).  An odd count is made even by a zero K-tile (the odometer closes the descriptors once the
         // K range is exhausted: no memory access, zeros in LDS, 2270 cycles of MFMAs on zeros) — worth it while that is a small price for

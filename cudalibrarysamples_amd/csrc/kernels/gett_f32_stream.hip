@@ -1049,7 +1049,7 @@ hipError_t launch_splitk_reduce_frag(const SplitKReduceParams& p, hipStream_t st
 // ---------------------------------------------------------------------------------------------
 // Kernel table
 // ---------------------------------------------------------------------------------------------
-// launches that took the flat entry since the library was loaded (host/api.cpp: ctamdFlatStartCount)
+// launches that took the flat entry since the library was loaded (host/exec_contraction.cpp: ctamdFlatStartCount)
 std::atomic<uint64_t> g_flatStartLaunches{0};
 
 // The flat entry's block, when the launch is one it covers: one output tile, one M and one N mode, no batch, a uniform split over whole

@@ -37,7 +37,7 @@
 // Every other tile (edges, strided D, a C without the 16-byte lanes of D, batch modes, split-K partials) takes the epilogues of
 // gett_h16w4x_kernel, in the ring, and is set up and staged behind them — slower than the one-tile kernel, which is why the planner
 // offers this kernel only to problems whose interior tiles can stream and cutensorContract launches the one-tile twin for beta != 0 with
-// such a C (plan_contraction.cpp, api.cpp).  Roofline and algorithmic bytes as in gett_h16v.hip (MFMA bf16; 2 M N K flop).
+// such a C (plan_contraction.cpp, exec_contraction.cpp).  Roofline and algorithmic bytes as in gett_h16v.hip (MFMA bf16; 2 M N K flop).
 #include <type_traits>
 
 #include "gett_h16x_common.h"

@@ -2,7 +2,7 @@
 every case and checks every draw, tests/test_gpu_composite_exact.py runs every case) — a helper module, not a conftest, the sibling of
 tests/exact_cases.py and tests/ew_exact_cases.py for
 
-  * cutensorContractTrinary   (api.cpp: two pairwise plans through an intermediate at the head of the workspace),
+  * cutensorContractTrinary   (exec_contraction.cpp: two pairwise plans through an intermediate at the head of the workspace),
   * cutensorBlockSparseContract (blocksparse.cpp: one dense plan per shape triple, contributions accumulated through D, untouched output
     blocks scaled or cleared),
   * cutensorPermute with CUTENSOR_OPERATION_DESCRIPTOR_PADDING_* (a fill of the whole padded buffer, then the inner plan at an element offset).

@@ -20,7 +20,7 @@ every output's sum) and asserted before anything is launched.
 exact_reference(): the integer result.  Small cases: numpy.einsum on int64 (complex: int64 planes).  Larger ones: an fp64 einsum — exact
 on this data in any order, so BLAS on the CPU or on the device both qualify — plus 4096 sampled outputs recomputed as plain int64 dot
 products that go through no BLAS.  Lone modes of 16-bit data (modes of one operand only) are reduced into a 16-bit temporary by the
-library (api.cpp, split_lone_modes): the reference rounds the exact lone-mode sum once to the data type, then contracts exactly.
+library (contraction_route.cpp, split_lone_modes): the reference rounds the exact lone-mode sum once to the data type, then contracts exactly.
 expected(): the exact value rounded once (to nearest even) to the output type, and the share of outputs that this rounding changes: at
 most 1 % for 16-bit outputs, none for the others; asserted on the reference, never on a kernel's result.
 

@@ -3,7 +3,7 @@ host-only.
 
 COMPUTE_DESC_32F on a contraction whose tensors are all real fp64 (all complex128) with double (complex double) scalars permits products
 of operands rounded once to fp32, on the fp32 MFMA.  Under CUTENSOR_AMD_F64X=force the planner takes that path whenever the descriptor
-permits it, under =0 never, and without the switch by its model (f64x_decide, api.cpp).  COMPUTE_DESC_64F, the 16-bit / TF32 descriptors
+permits it, under =0 never, and without the switch by its model (f64x_decide, contraction_route.cpp).  COMPUTE_DESC_64F, the 16-bit / TF32 descriptors
 on fp64 data, fp32 and complex64 data, and a caller who names a candidate are untouched."""
 import pytest
 

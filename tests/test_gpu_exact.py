@@ -12,7 +12,7 @@ its own time limit.
 
 16-bit outputs: the exact value is rounded once to the data type (at most 1 % of a case's outputs leave the type's exact integer range;
 those are compared with the single round-to-nearest-even of the exact value).  A result that differs there would be a second rounding:
-the one place where the library rounds twice by design is the lone-mode reduction of 16-bit data into a 16-bit temporary (api.cpp,
+the one place where the library rounds twice by design is the lone-mode reduction of 16-bit data into a 16-bit temporary (contraction_route.cpp,
 split_lone_modes) — bf16_lone_small_sums keeps those sums in the exact range, bf16_lone_rounded_sums takes them to about
 600 and asserts the result of rounding them first."""
 import pytest

@@ -196,7 +196,7 @@ if __name__ == "__main__":
 def test_beta_nonzero_on_a_plan_of_the_persistent_kernel(built):
     """beta is known only at the call.  Since round 6 the persistent kernel streams its tiles with beta != 0 too when C has the 16-byte
     lanes of D; with any other C every tile would take the ring-resident epilogue, where it is slower than its one-tile twin
-    (profiles/r05r_h16p_beta.jsonl), and cutensorContract launches the twin — same tile, same arguments (api.cpp; not when
+    (profiles/r05r_h16p_beta.jsonl), and cutensorContract launches the twin — same tile, same arguments (exec_contraction.cpp; not when
     CUTENSOR_AMD_H16_WAVES=4p names the kernel).  Here: the planner's own choice for a two-round shape, beta = 0 and beta != 0 through
     the SAME plan, against fp64, with the kernel that ran read back (ct.last_h16_kernel)."""
     import torch

@@ -1,4 +1,4 @@
-"""GPU parity of contractions whose operands are copied into packed temporaries first (api.cpp plan_repack, round 6): fp32 problems that
+"""GPU parity of contractions whose operands are copied into packed temporaries first (contraction_route.cpp plan_repack, round 6): fp32 problems that
 would leave the LDS-DMA ring kernels (a fastest contracted mode without whole 32-deep K-tiles beside further contracted modes; operands
 contiguous in DIFFERENT contracted modes — the reference's own test equation 'mlik,lkjm->lij', python/cutensor/torch/einsum_test.py:84-107)
 and their 16-bit twins (tests/test_gpu_h16.py holds those).  The copies are cutensorPermute at alpha = 1 — bit-exact — so the tolerance is

@@ -201,7 +201,7 @@ def test_persistent_kernel_only_where_its_tiles_can_stream(env):
 
 
 def test_workspace_contract_of_operands_copied_first(env):
-    """Round 6 (api.cpp plan_repack): a contraction whose operands the LDS-DMA kernels cannot stage as they lie asks
+    """Round 6 (contraction_route.cpp plan_repack): a contraction whose operands the LDS-DMA kernels cannot stage as they lie asks
     cutensorEstimateWorkspaceSize for its temporaries + the inner plan's need, plans the copies when that is granted
     (required <= estimate: contraction.cu:239 asserts it), and keeps the operands in place — the general family — when it is not."""
     ct, ops = env

@@ -1,4 +1,4 @@
-"""Plan memo (csrc/host/api.cpp cutensorCreatePlan): the einsum.cu flow creates descriptors + plan inside every call
+"""Plan memo (csrc/host/create_plan.cpp cutensorCreatePlan, csrc/host/plan_store.cpp): the einsum.cu flow creates descriptors + plan inside every call
 (cuTENSOR/einsum.cu:264-329) with the plan cache on (:443-445), so a repeated problem must be answered by a lookup.
 Host-only: planning needs no GPU."""
 import pytest
@@ -91,7 +91,7 @@ def test_reduction_and_permutation_plans_are_memoised_too(env):
 
 def test_two_step_plans_are_memoised_with_their_sub_plans(env):
     """Round 6: a contraction that reduces an operand over its lone modes first, or copies an operand into a packed temporary first
-    (api.cpp plan_repack: up to eight copy combinations priced per cutensorCreatePlan), is a plan that owns sub-plans — the memo
+    (contraction_route.cpp plan_repack: up to eight copy combinations priced per cutensorCreatePlan), is a plan that owns sub-plans — the memo
     keeps a deep copy and hands out deep copies; destroying one clone leaves the others (and the prototype) intact."""
     ct, ops = env
     h = ops.Handle(plan_cache=16)

@@ -27,7 +27,7 @@ SWEEP_CASES = [
     ("abcd,dcbe->ae", dict(a=4096, b=4, c=8, d=200, e=4096), "contracted extents 4 x 8 x 200 (four K-tiles per sweep, 78 % live)"),
     ("ijk,lkj->il", dict(i=4096, l=4096, j=16, k=72), "A contiguous in k, B in j"),
     ("abcd,dcbe->ae", dict(a=96, b=96, c=96, d=96, e=96), "the headline equation at extents of 96 (split-K)"),
-    # operands the LDS-DMA kernels cannot stage as they lie: copied into packed temporaries first (api.cpp plan_repack)
+    # operands the LDS-DMA kernels cannot stage as they lie: copied into packed temporaries first (contraction_route.cpp plan_repack)
     ("abcd,dcbe->ae", dict(a=2048, b=4, c=16, d=50, e=2048), "contracted extents 4 x 16 x 50: partial 16-byte units at the end of every sweep"),
     ("abcd,dcbe->ae", dict(a=2048, b=8, c=16, d=16, e=2048), "contracted extents 8 x 16 x 16: a quarter of every K-tile live"),
     ("mlik,lkjm->lij", dict(m=64, l=64, i=512, k=64, j=512), "the reference's test equation, larger: A contiguous in k, B in m"),
