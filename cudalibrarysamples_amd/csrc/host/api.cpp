@@ -348,9 +348,10 @@ cutensorStatus_t cutensorCreateReduction(const cutensorHandle_t handle, cutensor
     op.opReduce = opReduce;
     op.compute = descCompute;
     op.scalarType = scalar_type_for(op.A.desc.dtype, descCompute);
+    EwPlan ep;
     ReducePlan rp;
     std::string why;
-    st = plan_reduction(op, 0, handle->numCUs, rp, &why);   // validates the problem
+    st = plan_elementwise_any(op, 0, handle->numCUs, ep, rp, &why);   // validates the problem
     if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateReduction: %s", why.c_str()); return st; }
     const double es = (double)dtype_size(op.A.desc.dtype);
     op.flops = num_elements(op.A.desc);
@@ -373,8 +374,9 @@ cutensorStatus_t cutensorCreatePermutation(const cutensorHandle_t handle, cutens
     op.compute = descCompute;
     op.scalarType = scalar_type_for(op.A.desc.dtype, descCompute);
     EwPlan ep;
+    ReducePlan rp;
     std::string why;
-    st = plan_elementwise(op, ep, &why);
+    st = plan_elementwise_any(op, 0, handle->numCUs, ep, rp, &why);
     if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreatePermutation: %s", why.c_str()); return st; }
     op.movedBytes = (double)(dtype_size(op.A.desc.dtype) + dtype_size(op.D.desc.dtype)) * num_elements(op.D.desc);   // elementwise_permute.cu:208
     return new_op(desc, op);
@@ -399,8 +401,9 @@ cutensorStatus_t cutensorCreateElementwiseBinary(const cutensorHandle_t handle, 
     op.compute = descCompute;
     op.scalarType = scalar_type_for(op.A.desc.dtype, descCompute);
     EwPlan ep;
+    ReducePlan rp;
     std::string why;
-    st = plan_elementwise(op, ep, &why);
+    st = plan_elementwise_any(op, 0, handle->numCUs, ep, rp, &why);
     if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreateElementwiseBinary: %s", why.c_str()); return st; }
     op.movedBytes = (double)(dtype_size(op.A.desc.dtype) + 2 * dtype_size(op.D.desc.dtype)) * num_elements(op.D.desc);
     return new_op(desc, op);
@@ -579,8 +582,9 @@ cutensorStatus_t cutensorEstimateWorkspaceSize(const cutensorHandle_t handle, co
         return estimate_contraction(PlanRequest{handle, *desc, planPref, planPref ? *planPref : defaults, cap}, workspacePref, workspaceSizeEstimate);
     }
     if (desc->kind == OpKind::Reduction) {
+        EwPlan ep;
         ReducePlan rp;
-        const cutensorStatus_t st = plan_reduction(*desc, cap, handle->numCUs, rp, nullptr);
+        const cutensorStatus_t st = plan_elementwise_any(*desc, cap, handle->numCUs, ep, rp, nullptr);
         if (st != CUTENSOR_STATUS_SUCCESS) return st;
         *workspaceSizeEstimate = rp.workspace;
     }

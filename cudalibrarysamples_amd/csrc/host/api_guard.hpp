@@ -19,7 +19,7 @@
 #define CTAMD_API_CATCH_VOID catch (...) { }
 
 // Behaviour-changing environment switches exist for the test-suite and the measurement tools: CUTENSOR_AMD_H16_WAVES, _GEN, _NT, _PEEL,
-// _FUSED_FOLD, _FLAT_START, _F32_SPLITK, _H16P, _H16P_GRID, _H16_STRIPS, the measurement-only CUTENSOR_AMD_FORCE, _XCD_BALANCE, _KORDER, _ABLATION, _H16_SPLITK,
+// _FUSED_FOLD, _FLAT_START, _F32_SPLITK, _H16P, _H16P_GRID, _H16_STRIPS, _EW_TABLE, the measurement-only CUTENSOR_AMD_FORCE, _XCD_BALANCE, _KORDER, _ABLATION, _H16_SPLITK,
 // _H16_TRANSPOSE_T1, and CUTENSORMG_AMD_{ASSUME_RCCL,DIRECT,PEEL,QSPLIT,SHARD2,TEST_DROP_WAITS}, CUTENSORMP_AMD_ALGO.  They are read only
 // by the TEST-HOOKS flavour of the libraries (make HOOKS=1 -> lib_hooks/, what tests/ and the tools load).  In the production libraries
 // (lib/) the macro is a null pointer and the names do not even appear as strings:

@@ -421,7 +421,7 @@ bool plan_env_override() {
            CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_TRANSPOSE_T1") || CTAMD_HOOK_ENV("CUTENSOR_AMD_NT") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_WAVES") || CTAMD_HOOK_ENV("CUTENSOR_AMD_H16_SPLITK") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_KORDER") || CTAMD_HOOK_ENV("CUTENSOR_AMD_ABLATION") || CTAMD_HOOK_ENV("CUTENSOR_AMD_PEEL") || CTAMD_HOOK_ENV("CUTENSOR_AMD_GEN") ||
            CTAMD_HOOK_ENV("CUTENSOR_AMD_REPACK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_ANY") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32X") ||
-           CTAMD_HOOK_ENV("CUTENSOR_AMD_F64X") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32_SPLITK");
+           CTAMD_HOOK_ENV("CUTENSOR_AMD_F64X") || CTAMD_HOOK_ENV("CUTENSOR_AMD_F32_SPLITK") || CTAMD_HOOK_ENV("CUTENSOR_AMD_EW_TABLE");
 }
 // CUTENSOR_AMD_GEN=0 (hooks flavour): never the general MFMA family
 static bool gen_family_off() { return CTAMD_HOOK_ENV_IS("CUTENSOR_AMD_GEN", '0'); }

@@ -530,8 +530,9 @@ static cutensorStatus_t build_padded_permutation(const PlanRequest& rq, cutensor
 static cutensorStatus_t build_elementwise(const PlanRequest& rq, cutensorPlan& pl) {
     const cutensorOperationDescriptor& desc = rq.desc;
     if (desc.kind == OpKind::Reduction) {
-        const cutensorStatus_t st = plan_reduction(desc, rq.wsLimit, rq.handle->numCUs, pl.red, nullptr);
-        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        std::string why;
+        const cutensorStatus_t st = plan_elementwise_any(desc, rq.wsLimit, rq.handle->numCUs, pl.ew, pl.red, &why);
+        if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreatePlan: %s", why.c_str()); return st; }
         pl.requiredWorkspace = pl.red.workspace;
         CT_LOG("plan: reduction variant=%d kept=%u red=%u splitR=%u perm=%d", pl.red.variant, pl.red.p.kept.total, pl.red.p.red.total, pl.red.p.splitR,
                (int)pl.red.isPermutation);
@@ -542,8 +543,9 @@ static cutensorStatus_t build_elementwise(const PlanRequest& rq, cutensorPlan& p
         CT_LOG("plan: elementwise trinary passes=%d swapAB=%d bothPermuted=%d variant(last)=%d", pl.ew3.twoPass ? 2 : 1, (int)pl.ew3.swapAB,
                (int)pl.ew3.bothPermuted, pl.ew3.last.variant);
     } else {
-        const cutensorStatus_t st = plan_elementwise(desc, pl.ew, nullptr);
-        if (st != CUTENSOR_STATUS_SUCCESS) return st;
+        std::string why;
+        const cutensorStatus_t st = plan_elementwise_any(desc, rq.wsLimit, rq.handle->numCUs, pl.ew, pl.red, &why);
+        if (st != CUTENSOR_STATUS_SUCCESS) { CT_LOG("cutensorCreatePlan: %s", why.c_str()); return st; }
         CT_LOG("plan: elementwise variant=%d E0=%u E1=%u rest=%u blocks=%u", pl.ew.variant, pl.ew.p.E0, pl.ew.p.E1, pl.ew.p.rest.total, pl.ew.p.nBlocks);
     }
     return CUTENSOR_STATUS_SUCCESS;

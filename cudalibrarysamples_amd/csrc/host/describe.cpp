@@ -2,6 +2,7 @@
 // bench): ctamdDescribePlan for contraction plans (element-wise and reduction plans: exec_elementwise.cpp, block-sparse ones:
 // blocksparse.cpp), what cuTENSORMg asks about a plan, and the counts of kernels and candidates.
 #include <cstdio>
+#include <cstring>
 
 #include <hip/hip_runtime.h>
 
@@ -127,6 +128,20 @@ static int describe_inner(const cutensorPlan& plan, char* buf, size_t len, int n
     buf[n - 1] = ',';
     return n - 1 + m;
 }
+
+// The mode table of an element-wise or reduction plan on the kernels of elementwise_table.hip, byte for byte as a launch passes it
+// (pointers and scalars zero): what tests/harness/ew_table_layout_harness.cpp walks on the CPU.  Returns sizeof(EwTable), 0 for a plan
+// that has none, -1 for a buffer too small.
+int ctamdEwTable(const cutensorPlan_t plan, void* buf, size_t len) try {
+    if (plan == nullptr || buf == nullptr) return -1;
+    const EwTable* tab = nullptr;
+    if (plan->kind == OpKind::Reduction) tab = plan->red.isPermutation ? plan->red.perm.tab.get() : plan->red.tab.get();
+    else if (plan->kind == OpKind::Permutation || plan->kind == OpKind::ElementwiseBinary) tab = plan->ew.tab.get();
+    if (tab == nullptr) return 0;
+    if (len < sizeof(EwTable)) return -1;
+    std::memcpy(buf, tab, sizeof(EwTable));
+    return (int)sizeof(EwTable);
+} CTAMD_API_CATCH_INT
 
 // 1 when this library reads the test / measurement switches (CTAMD_HOOK_ENV: the lib_hooks/ flavour)
 int ctamdTestHooksBuilt(void) try { return CTAMD_HOOKS_BUILT; } CTAMD_API_CATCH_INT

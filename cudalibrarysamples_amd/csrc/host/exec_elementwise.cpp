@@ -17,7 +17,19 @@ static bool reads_c(const EwPlan& ew, CxScalar gamma) {
     return ew.usesC && (gamma.re != 0.0 || gamma.im != 0.0 || (ew.p.opAC != 0 && ew.p.opAC != CUTENSOR_OP_ADD));
 }
 
+// a plan on the mode table (elementwise_table.hip): the table by value, pointers and scalars written per launch
+static hipError_t run_elementwise_table(const EwPlan& ew, hipDataType dtype, const EwCall& c, hipStream_t stream) {
+    if (!ew.tab || c.X != nullptr || c.E != nullptr) return hipErrorInvalidValue;      // (the trinary planner never gets this variant)
+    EwTable t = *ew.tab;
+    t.A = c.A; t.D = c.D;
+    t.C = reads_c(ew, c.gamma) ? c.C : nullptr;
+    t.alpha64 = c.alpha.re; t.alphaIm = c.alpha.im;
+    t.gamma64 = c.gamma.re; t.gammaIm = c.gamma.im;
+    return launch_elementwise_table(t, (int)dtype, ew.tabGrid, stream);
+}
+
 hipError_t run_elementwise(const EwPlan& ew, hipDataType dtype, const EwCall& c, hipStream_t stream) {
+    if (ew.on_table()) return run_elementwise_table(ew, dtype, c, stream);
     Ew2DParams p = ew.p;
     p.A = c.A; p.X = c.X; p.E = c.E; p.D = c.D;
     p.C = reads_c(ew, c.gamma) ? c.C : nullptr;
@@ -87,7 +99,14 @@ static int describe_unary(char* buf, size_t len, int n, int32_t a, int32_t b, in
 
 int describe_elementwise(const cutensorPlan& pl, char* buf, size_t len) {
     int n = 0;
-    if (pl.kind == OpKind::Reduction && !pl.red.isPermutation) {
+    if (pl.kind == OpKind::Reduction && !pl.red.isPermutation && pl.red.variant == RED_TABLE) {
+        // the fields of every reduction plan, then the mode table's: the modes of the view (kept + reduced) and the kernel
+        n = std::snprintf(buf, len, "{\"op\":\"reduction\",\"variant\":%d,\"kept\":%u,\"red\":%u,\"splitR\":%u,\"redPerSplit\":%u,\"rowAny\":0,\"workspace\":%llu,"
+                          "\"modes\":%u,\"keptModes\":%u,\"kname\":\"reduce_table_kernel\"}",
+                          pl.red.variant, pl.red.p.kept.total, pl.red.p.red.total, pl.red.p.splitR, pl.red.p.redPerSplit,
+                          (unsigned long long)pl.requiredWorkspace, pl.red.tab->nModes, pl.red.tab->nKept);
+        n = describe_unary(buf, len, n, pl.red.p.unA, 0, pl.red.p.unC);
+    } else if (pl.kind == OpKind::Reduction && !pl.red.isPermutation) {
         n = std::snprintf(buf, len, "{\"op\":\"reduction\",\"variant\":%d,\"kept\":%u,\"red\":%u,\"splitR\":%u,\"redPerSplit\":%u,\"rowAny\":%u,\"workspace\":%llu}",
                           pl.red.variant, pl.red.p.kept.total, pl.red.p.red.total, pl.red.p.splitR, pl.red.p.redPerSplit,
                           pl.red.p.rowAny, (unsigned long long)pl.requiredWorkspace);
@@ -111,6 +130,15 @@ int describe_elementwise(const cutensorPlan& pl, char* buf, size_t len) {
             n = n - 1 + std::snprintf(buf + n - 1, len - (size_t)n + 1, ",\"conj\":[%d,%d,%d]}", (int)conj(r.a), (int)conj(r.b), (int)q.conjC);
     } else {
         const EwPlan& e = (pl.kind == OpKind::Reduction) ? pl.red.perm : pl.ew;
+        if (e.on_table()) {
+            // a plan on the mode table: "modes" of the view, "tile" = [positions of a tile, modes taken from A's side, from D's side]
+            // (zeros on the gather kernel), "blocks" = tiles (gather kernel: elements), the workgroups launched, the tile kernel's LDS
+            const bool tiled = e.variant == EW_TABLE_TILE;
+            n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"modes\":%u,\"tile\":[%u,%u,%u],\"kname\":\"%s\",\"blocks\":%u,\"grid\":%u,\"lds\":%u}",
+                              e.variant, e.tab->nModes, e.tab->tilePos, e.tabFromA, e.tabFromD, tiled ? "ew_table_tile_kernel" : "ew_table_gather_kernel",
+                              e.tab->total, e.tabGrid, tiled ? ew_table_lds_bytes((uint32_t)dtype_size(e.dtypeD)) : 0u);
+            return describe_unary(buf, len, n, e.p.unA, 0, e.p.unC);
+        }
         n = std::snprintf(buf, len, "{\"op\":\"elementwise\",\"variant\":%d,\"E0\":%u,\"E1\":%u,\"rest\":%u,\"blocks\":%u,\"tile0\":%u,\"order\":%u}",
                           e.variant, e.p.E0, e.p.E1, e.p.rest.total, e.p.nBlocks, e.p.tile0, e.p.order);
         n = describe_unary(buf, len, n, e.p.unA, 0, e.p.unC);
@@ -146,6 +174,15 @@ cutensorStatus_t cutensorReduce(const cutensorHandle_t handle, const cutensorPla
         EwCall call;
         call.A = A; call.alpha = a; call.C = C; call.gamma = b; call.D = D;
         err = run_elementwise(plan->red.perm, plan->dtype, call, stream);
+    } else if (plan->red.variant == RED_TABLE) {
+        if (plan->requiredWorkspace > 0 && (workspace == nullptr || workspaceSize < plan->requiredWorkspace))
+            return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;
+        if (!plan->red.tab) return CUTENSOR_STATUS_INTERNAL_ERROR;
+        EwTable t = *plan->red.tab;
+        t.A = A; t.C = betaSet ? C : nullptr; t.D = D;
+        t.alpha64 = a.re; t.alphaIm = a.im; t.gamma64 = b.re; t.gammaIm = b.im;
+        t.partial = (t.splitR > 1) ? workspace : nullptr;
+        err = launch_reduce_table(t, (int)plan->dtype, plan->accumulate64 || plan->dtype == HIP_R_64F, stream);
     } else {
         if (plan->requiredWorkspace > 0 && (workspace == nullptr || workspaceSize < plan->requiredWorkspace))
             return CUTENSOR_STATUS_INSUFFICIENT_WORKSPACE;

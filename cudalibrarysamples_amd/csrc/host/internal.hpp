@@ -22,6 +22,7 @@
 // _KORDER, _ABLATION, _H16_SPLITK, _H16_TRANSPOSE_T1).  The production library reads CUTENSOR_LOG_LEVEL and nothing else.
 #include "../kernels/launch.h"
 #include "../kernels/params.h"
+#include "../kernels/ew_table_layout.h"
 
 // The ABI names these structs only as opaque pointer targets (cutensor/types.h).
 struct cutensorComputeDescriptor {
@@ -181,6 +182,13 @@ struct EwPlan {
     // rides along as E — Ew2DParams, the argument block of the other kernels, has no field for either (run_elementwise hands them over
     // in an Ew3CplxExtras)
     int32_t    conjX = 0, conjE = 0;
+    // variants EW_TABLE_TILE / EW_TABLE_GATHER (more unfusable modes than `p` describes; plan_elementwise_table.cpp): the mode table the
+    // kernels of elementwise_table.hip take by value, finished at plan time except for pointers and scalars — immutable, shared with
+    // the plan's copies — and the launch's grid
+    std::shared_ptr<const EwTable> tab;
+    uint32_t   tabGrid = 0;
+    uint32_t   tabFromA = 0, tabFromD = 0;   // tile kernel: how many modes the tile took from A's side and from D's (the description's "tile")
+    bool on_table() const { return variant == EW_TABLE_TILE || variant == EW_TABLE_GATHER; }
 };
 // cutensorElementwiseTrinaryExecute: D = opABC(opAB(alpha A, beta B), gamma C) as one or two passes of the
 // element-wise kernels (plan_elementwise_trinary)
@@ -203,14 +211,42 @@ struct ReducePlan {
     uint64_t     workspace = 0;
     bool         isPermutation = false;   // no reduced modes: executed by the element-wise family
     EwPlan       perm;
+    // variant RED_TABLE (a kept or reduced group of more than kMaxGroupModes digits): the mode table of reduce_table_kernel; `p` then
+    // holds the totals, the split and the operators for the description, and no digits
+    std::shared_ptr<const EwTable> tab;
 };
+
+// One mode of an element-wise or reduction problem while it is planned: extent and element strides per tensor
+struct EwMode {
+    int64_t extent;
+    int64_t sA = 0, sD = 0, sC = 0;
+    int64_t sX = 0;   // second permuted operand (element-wise trinary), 0 when unused
+};
+// Set by plan_elementwise / plan_reduction where they refuse a problem for its MODE COUNT alone ("too many unfusable modes", "mode
+// group too large") — every other check passed: the fused modes they got as far as, for the mode-table route to start from.
+// plan_elementwise: `modes`, sorted by D's stride; plan_reduction: `kept` and `red`, each sorted by A's stride.
+struct ModeCountRefusal {
+    bool hit = false;
+    std::vector<EwMode> modes, kept, red;
+};
+// the code a kernel gets for an operand's unary operator: 0 for the operators that leave real data as it is
+inline bool unary_is_plain(cutensorOperator_t o) { return o == CUTENSOR_OP_IDENTITY || o == CUTENSOR_OP_CONJ; }
+inline int32_t unary_code(cutensorOperator_t o) { return unary_is_plain(o) ? 0 : (int32_t)o; }
 
 // allowWide = false: never the tiled kernels of 8- / 16-byte elements (the trinary planner on real data: they take no E / X operand; on
 // complex data its passes run on kernels of their own that do, and it allows them)
-cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan& plan, std::string* why, bool allowWide = true);
+cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan& plan, std::string* why, bool allowWide = true,
+                                  ModeCountRefusal* over = nullptr);
 cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& op, EwTrinaryPlan& plan, std::string* why);
 cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t wsLimit, int numCUs,
-                                ReducePlan& plan, std::string* why);
+                                ReducePlan& plan, std::string* why, ModeCountRefusal* over = nullptr);
+// The planner of the PUBLIC permutation, binary and reduction descriptors (cutensorCreatePermutation / ElementwiseBinary / Reduction,
+// cutensorEstimateWorkspaceSize, cutensorCreatePlan): plan_elementwise / plan_reduction, and exactly where those refuse a problem for
+// its mode count, the mode-table route (plan_elementwise_table.cpp).  Fills `red` for a reduction descriptor, `ew` for the others.
+// The planner's internal callers (trinary passes, repack, lone-mode reductions, padded permutations) keep calling the two above.
+cutensorStatus_t plan_elementwise_any(const cutensorOperationDescriptor& op, uint64_t wsLimit, int numCUs, EwPlan& ew, ReducePlan& red,
+                                      std::string* why);
+bool ew_table_gather_forced();   // CUTENSOR_AMD_EW_TABLE=gather (hooks flavour): the gather kernel where the tile kernel applies
 
 // ---- execute (exec_elementwise.cpp: the entry points of this family and the one path from a plan to a launch) ----------------
 struct CxScalar { double re = 0.0, im = 0.0; };

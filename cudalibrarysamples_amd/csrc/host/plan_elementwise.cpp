@@ -16,12 +16,6 @@ namespace ctamd {
 
 namespace {
 
-struct EwMode {
-    int64_t extent;
-    int64_t sA = 0, sD = 0, sC = 0;
-    int64_t sX = 0;   // second permuted operand (element-wise trinary), 0 when unused
-};
-
 int find_label(const std::vector<int32_t>& modes, int32_t l) {
     for (size_t i = 0; i < modes.size(); ++i)
         if (modes[i] == l) return (int)i;
@@ -54,7 +48,6 @@ void fuse(std::vector<EwMode>& g, bool useC) {
 
 // Unary operator of an operand (kernels/unary_op.h): IDENTITY / CONJ on every data type; SQRT, RELU, RCP, SIGMOID, TANH, EXP, LOG, ABS and
 // NEG on real floating-point data.  Returns nullptr when the operator is admitted, else why it is not.
-bool unary_is_plain(cutensorOperator_t o) { return o == CUTENSOR_OP_IDENTITY || o == CUTENSOR_OP_CONJ; }
 const char* unary_refusal(cutensorOperator_t o, hipDataType dtype) {
     if (unary_is_plain(o)) return nullptr;
     switch (o) {
@@ -66,9 +59,6 @@ const char* unary_refusal(cutensorOperator_t o, hipDataType dtype) {
     if (dtype != HIP_R_32F && dtype != HIP_R_64F && dtype != HIP_R_16F && dtype != HIP_R_16BF) return "unary operators need floating-point data";
     return nullptr;
 }
-// the code a kernel gets: 0 for the operators that leave real data as it is
-int32_t unary_code(cutensorOperator_t o) { return unary_is_plain(o) ? 0 : (int32_t)o; }
-
 bool fill_rest(ModeGroup& g, const std::vector<EwMode>& modes) {
     std::memset(&g, 0, sizeof(g));
     if ((int)modes.size() > kMaxGroupModes) return false;
@@ -89,7 +79,7 @@ bool fill_rest(ModeGroup& g, const std::vector<EwMode>& modes) {
 
 }  // namespace
 
-cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan& plan, std::string* why, bool allowWide) {
+cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan& plan, std::string* why, bool allowWide, ModeCountRefusal* over) {
     auto fail = [&](cutensorStatus_t st, const char* msg) {
         if (why) *why = msg;
         return st;
@@ -223,7 +213,10 @@ cutensorStatus_t plan_elementwise(const cutensorOperationDescriptor& op, EwPlan&
         for (size_t i = 1; i < modes.size(); ++i)
             if ((int)i != i1) rest.push_back(modes[i]);
     }
-    if (!fill_rest(p.rest, rest)) return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "too many unfusable modes");
+    if (!fill_rest(p.rest, rest)) {
+        if (over != nullptr && rest.size() > (size_t)kMaxGroupModes) { over->hit = true; over->modes = modes; }
+        return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "too many unfusable modes");
+    }
     for (size_t i = 0; i < rest.size(); ++i) p.restX[i] = rest[i].sX;
 
     plan.dtypeA = A.desc.dtype;
@@ -523,7 +516,7 @@ cutensorStatus_t plan_elementwise_trinary(const cutensorOperationDescriptor& opI
 }
 
 cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t wsLimit, int numCUs,
-                                ReducePlan& plan, std::string* why) {
+                                ReducePlan& plan, std::string* why, ModeCountRefusal* over) {
     auto fail = [&](cutensorStatus_t st, const char* msg) {
         if (why) *why = msg;
         return st;
@@ -571,7 +564,7 @@ cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t 
         e.opReduce = CUTENSOR_OP_ADD;   // nothing is reduced: opReduce (MAX / MIN / MUL) must not become the A-with-C combiner
         e.C.present = true;
         plan.isPermutation = true;
-        return plan_elementwise(e, plan.perm, why);
+        return plan_elementwise(e, plan.perm, why, true, over);
     }
     auto bySA = [](const EwMode& x, const EwMode& y) { return x.sA < y.sA; };
     std::stable_sort(kept.begin(), kept.end(), bySA);
@@ -591,8 +584,10 @@ cutensorStatus_t plan_reduction(const cutensorOperationDescriptor& op, uint64_t 
     }
     ReduceParams& p = plan.p;
     std::memset(&p, 0, sizeof(p));
-    if (!fill_rest(p.kept, kept) || !fill_rest(p.red, red))
+    if (!fill_rest(p.kept, kept) || !fill_rest(p.red, red)) {
+        if (over != nullptr && (kept.size() > (size_t)kMaxGroupModes || red.size() > (size_t)kMaxGroupModes)) { over->hit = true; over->kept = kept; over->red = red; }
         return fail(CUTENSOR_STATUS_NOT_SUPPORTED, "mode group too large");
+    }
     p.op = rop;
     p.conjA = (cplx && A.op == CUTENSOR_OP_CONJ) ? 1 : 0;
     p.conjC = (cplx && C.op == CUTENSOR_OP_CONJ) ? 1 : 0;

@@ -123,8 +123,11 @@ enum EwVariant : int {
     EW_ROWCOPY   = 1,  // sD0 == 1 and sA0 == 1: 16-byte lanes along dim0, no LDS
     EW_GENERIC   = 2,  // any strides, any dtype: one element per lane
     EW_TRANSPOSE_ANY = 4,  // pure permutation of 2- / 4-byte elements, D contiguous along dim0 and A along dim1, any extents / alignment: 64 x 64 LDS tile, element-wise
-    EW_BLOCK     = 3   // pure permutation of 2- / 4-byte elements whose leading modes are the same packed set in A and D: contiguous blocks
+    EW_BLOCK     = 3,  // pure permutation of 2- / 4-byte elements whose leading modes are the same packed set in A and D: contiguous blocks
                        // through LDS, permuted inside (Ew2DParams::blk*); falls back to EW_GENERIC when a C / E / X operand is attached
+    // more unfusable modes than Ew2DParams describes (elementwise_table.hip, on an EwTable instead):
+    EW_TABLE_TILE   = 5,   // A and D each have a stride-1 mode, A carries every mode of D: tiles through LDS, read in A's order, written in D's
+    EW_TABLE_GATHER = 6    // anything else: one output element per lane, every digit decoded
 };
 // Grid of a tiled element-wise launch.  One workgroup per tile: a workgroup that loops over tiles serialises its own read -> barrier ->
 // write phases, fresh workgroups overlap them across the CU (2048^3 permutation, 64 x 64 tiles: 5.37 TB/s with the grid capped at 32 Ki
@@ -153,9 +156,17 @@ hipError_t launch_fill(void* D, uint64_t n, int dtype, double value, hipStream_t
 enum ReduceVariant : int {
     RED_COL     = 0,   // A's stride-1 mode is kept: lanes along it (float4), loop over reduced modes
     RED_ROW     = 1,   // A's stride-1 mode is reduced: one workgroup per kept element
-    RED_GENERIC = 2    // any strides, any dtype
+    RED_GENERIC = 2,   // any strides, any dtype
+    RED_TABLE   = 3    // a kept or reduced group of more than kMaxGroupModes digits (elementwise_table.hip, on an EwTable)
 };
 hipError_t launch_reduce(const ReduceParams& p, int variant, int dtype, bool acc64, hipStream_t stream);
 hipError_t launch_reduce_finalize(const ReduceParams& p, int dtype, bool acc64, hipStream_t stream);
+
+// the mode-table kernels (elementwise_table.hip; the table: ew_table_layout.h).  Element-wise: the tile or the gather kernel by
+// EwTable::kind on `grid` workgroups, each looping over tiles / elements.  Reduction: reduce_table_kernel and, when the table carries
+// partials (splitR > 1), reduce_table_finalize_kernel behind it.
+struct EwTable;
+hipError_t launch_elementwise_table(const EwTable& t, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_reduce_table(const EwTable& t, int dtype, bool acc64, hipStream_t stream);
 
 }  // namespace ctamd

@@ -60,7 +60,22 @@ struct WF64 {
     __device__ static __forceinline__ Acc shfl_down(Acc v, int off) { return __shfl_down(v, off, 64); }
 };
 
-// ---- bf16 / fp16 (reductions: fp32 accumulation) ----------------------------------------------------------------------------------
+// ---- fp32, one element at a time (the mode-table kernels, elementwise_table.hip: every data type through one traits interface) -----------
+// ACC = double: fp32 data accumulated in 64 bits (a reduction under COMPUTE_DESC_64F)
+template <typename ACC>
+struct WF32 {
+    typedef float Elem;
+    typedef ACC Acc;
+    static constexpr int NV = 4;
+    static constexpr bool CX = false;
+    __device__ static __forceinline__ Acc identity(int op) { return w_real_identity<Acc>(op); }
+    __device__ static __forceinline__ Acc apply(int op, Acc a, Acc b) { return w_real_apply<Acc>(op, a, b); }
+    __device__ static __forceinline__ Acc load1(const Elem* q, bool) { return (Acc)*q; }
+    __device__ static __forceinline__ void store1(Elem* q, Acc v) { *q = (float)v; }
+    __device__ static __forceinline__ Acc scale(double re, double, Acc x) { return (Acc)re * x; }
+};
+
+// ---- bf16 / fp16 (reductions: fp32 accumulation)----------------------------------------------------------------------------------
 template <bool BF>
 struct WH16 {
     typedef uint16_t Elem;

@@ -1,7 +1,19 @@
 // mp_copy.cpp — strided copies of boxes through the single-GPU ABI: an identity cutensorPermute per launch.
+#include <cstring>
+
 #include "mp_internal.hpp"
 
+extern "C" int ctamdDescribePlan(const cutensorPlan_t plan, char* buf, size_t len);   // libcutensor.so diagnostic
+
 namespace ctamd_mp CTAMD_MP_HIDDEN {
+
+// A copy of more unfusable modes than the tiled element-wise kernels describe used to be refused, and make_copy peels modes until one
+// is not; the single-GPU library now plans such a copy on its mode-table kernels instead.  The launch counts of this library's plans
+// are pinned, so a plan on those kernels is still the refusal it used to be — exactly so: that route starts only where the refusal was.
+static bool on_mode_table(cutensorPlan_t plan) {
+    char text[1024];
+    return ctamdDescribePlan(plan, text, sizeof(text)) > 0 && std::strstr(text, "\"kname\":\"ew_table_") != nullptr;
+}
 
 static cutensorStatus_t try_copy_plan(cutensorHandle_t h, hipDataType dtype, const std::vector<CMode>& modes, uint32_t alignSrc, uint32_t alignDst,
                                       EnginePlan& plan) {
@@ -20,6 +32,11 @@ static cutensorStatus_t try_copy_plan(cutensorHandle_t h, hipDataType dtype, con
         st = cutensorCreatePermutation(h, &tmp.op, tmp.desc[0], lab.data(), CUTENSOR_OP_IDENTITY, tmp.desc[1], lab.data(),
                                        rt == HIP_R_64F ? CUTENSOR_COMPUTE_DESC_64F : CUTENSOR_COMPUTE_DESC_32F);
     if (st == CUTENSOR_STATUS_SUCCESS) st = cutensorCreatePlan(h, &raw, tmp.op, nullptr, 0);
+    if (st == CUTENSOR_STATUS_SUCCESS && on_mode_table(raw)) {
+        cutensorDestroyPlan(raw);
+        raw = nullptr;
+        st = CUTENSOR_STATUS_NOT_SUPPORTED;
+    }
     plan.reset(raw);
     return st;
 }
