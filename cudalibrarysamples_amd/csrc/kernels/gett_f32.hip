@@ -39,6 +39,7 @@
 #include "params.h"
 #include "launch.h"
 #include "gett_common.h"
+#include "round16.h"
 
 namespace ctamd {
 
@@ -761,17 +762,18 @@ __global__ void __launch_bounds__(512) splitk_reduce_kernel(const SplitKReducePa
         static_cast<float*>(p.D)[oDl + oDm + oDn] = val;
     } else {   // 16-bit data of the gett_h16 kernels: fp32 partials, one rounding of the result
         const bool bf = p.outType == 1;
+        uint16_t c = 0;
         if (p.beta != 0.f) {
-            const uint16_t c = static_cast<const uint16_t*>(p.C)[oCl + oCm + oCn];
-            val += p.beta * (bf ? __uint_as_float((uint32_t)c << 16) : (float)__builtin_bit_cast(_Float16, c));
+            c = static_cast<const uint16_t*>(p.C)[oCl + oCm + oCn];
+            if (bf) val += p.beta * __uint_as_float((uint32_t)c << 16);
         }
         uint16_t out;
         if (bf) {
             uint32_t u = __float_as_uint(val);
             if ((u & 0x7fffffffu) > 0x7f800000u) out = (uint16_t)((u >> 16) | 0x40u);
             else { u += 0x7fffu + ((u >> 16) & 1u); out = (uint16_t)(u >> 16); }
-        } else {
-            out = __builtin_bit_cast(uint16_t, (_Float16)val);
+        } else {   // fp16: val + beta * c rounded once (round16.h)
+            out = p.beta != 0.f ? h_round16_with_c<false>(val, p.beta, c) : h_round16<false>(val);
         }
         static_cast<uint16_t*>(p.D)[oDl + oDm + oDn] = out;
     }
@@ -830,12 +832,13 @@ __global__ void __launch_bounds__(256) splitk_reduce_wide_kernel(const SplitKRed
     }
     const bool bf = p.outType == 1;
     uint16_t* D = static_cast<uint16_t*>(p.D) + oD;
+    uint16_t c[4] = {0, 0, 0, 0};
     if (p.beta != 0.f) {
         const uint16_t* C = static_cast<const uint16_t*>(p.C) + oC;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint16_t c = C[dC[i]];
-            val[i] += p.beta * (bf ? __uint_as_float((uint32_t)c << 16) : (float)__builtin_bit_cast(_Float16, c));
+            c[i] = C[dC[i]];
+            if (bf) val[i] += p.beta * __uint_as_float((uint32_t)c[i] << 16);
         }
     }
     uint16_t out[4];
@@ -845,8 +848,8 @@ __global__ void __launch_bounds__(256) splitk_reduce_wide_kernel(const SplitKRed
             uint32_t u = __float_as_uint(val[i]);
             if ((u & 0x7fffffffu) > 0x7f800000u) out[i] = (uint16_t)((u >> 16) | 0x40u);
             else { u += 0x7fffu + ((u >> 16) & 1u); out[i] = (uint16_t)(u >> 16); }
-        } else {
-            out[i] = __builtin_bit_cast(uint16_t, (_Float16)val[i]);
+        } else {   // fp16: val + beta * c rounded once (round16.h)
+            out[i] = p.beta != 0.f ? h_round16_with_c<false>(val[i], p.beta, c[i]) : h_round16<false>(val[i]);
         }
     }
     if (vecD && (reinterpret_cast<uintptr_t>(D) & 7u) == 0u) {

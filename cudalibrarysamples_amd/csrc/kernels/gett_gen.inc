@@ -31,6 +31,7 @@
 //
 // Included by gett_gen_h16.hip / gett_gen_f64.hip / gett_gen_cplx.hip, which instantiate their part of the table.
 #include "gett_gen_common.h"
+#include "round16.h"
 
 namespace ctamd {
 
@@ -396,15 +397,9 @@ __global__ void __launch_bounds__(256, 2) gett_gen_kernel(const GettParams p) {
                 const int64_t oD = offDm + offDn[j], oC = offCm + offCn[j];
                 if constexpr (ES == 2) {
                     constexpr bool BF = GE == GEN_BF16;
-                    float val = p.alpha * acc[i][j].v[t];
-                    if (p.beta != 0.f) {
-                        const uint16_t c = static_cast<const uint16_t*>(p.C)[oC];
-                        val += p.beta * (BF ? __uint_as_float((uint32_t)c << 16) : (float)__builtin_bit_cast(_Float16, c));
-                    }
-                    uint16_t out;
-                    if constexpr (BF) out = __builtin_bit_cast(uint16_t, (__bf16)val);      // round to nearest even, NaN stays NaN
-                    else              out = __builtin_bit_cast(uint16_t, (_Float16)val);
-                    static_cast<uint16_t*>(p.D)[oD] = out;
+                    const float val = p.alpha * acc[i][j].v[t];      // one rounding of val + beta * c: round16.h
+                    static_cast<uint16_t*>(p.D)[oD] = p.beta != 0.f ? h_round16_with_c<BF>(val, p.beta, static_cast<const uint16_t*>(p.C)[oC])
+                                                                      : h_round16<BF>(val);
                 } else if constexpr (GE == GEN_F64) {
                     double val = p.alpha64 * acc[i][j].v[t];
                     if (p.beta64 != 0.0) val += p.beta64 * static_cast<const double*>(p.C)[oC];

@@ -17,6 +17,7 @@
 #include "params.h"
 #include "launch.h"
 #include "gett_common.h"
+#include "round16.h"
 
 namespace ctamd {
 
@@ -103,35 +104,7 @@ __device__ __forceinline__ uint16_t h_from_float(float f, bool bf) {
 // contiguous and 16-byte aligned in D (and in C when beta != 0): checked once per workgroup (wave-uniform); otherwise a rolled
 // element-wise loop stores from the same LDS image with any strides.
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool BF>
-__device__ __forceinline__ uint16_t h_round16(float f) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (BF) return __builtin_bit_cast(uint16_t, (__bf16)f);      // round to nearest even, NaN stays NaN
-    else              return __builtin_bit_cast(uint16_t, (_Float16)f);
-#else
-    (void)f; return 0;
-#endif
-}
-
-// round16(v + beta * c), c a 16-bit value of the tensor's type, with ONE rounding (round 6).  bf16: the fma is an fp32 operation whatever
-// the compiler makes of it (v_fma_f32 / v_pk_fma_f32), then one conversion.  fp16: v_fma_mixlo_f16 by hand — the sum is rounded once,
-// straight to 16 bits.  Written as `v += beta * (float)c; (_Float16)v` the compiler picks per element between that instruction and
-// v_pk_fma_f32 + v_cvt_pk_f16_f32 (an fp32 sum rounded a second time), depending on how the neighbours vectorise: two kernels of one plan
-// (gett_h16w4x_kernel / gett_h16w4p_kernel) then differ in the last bit of a few results per million (profiles/r06w, r06x).
-template <bool BF>
-__device__ __forceinline__ uint16_t h_round16_with_c(float v, float beta, uint16_t c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (BF) return h_round16<true>(__builtin_fmaf(beta, __uint_as_float((uint32_t)c << 16), v));
-    else {
-        uint32_t r;
-        const uint32_t cw = c;
-        asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(beta), "v"(cw), "v"(v));
-        return (uint16_t)r;
-    }
-#else
-    (void)v; (void)beta; (void)c; return 0;
-#endif
-}
+// h_round16 / h_round16_with_c: round16.h (shared with the split-K folds, the general family and gett_simple.hip)
 template <bool BF>
 __device__ __forceinline__ s16x8 h_round8(const f32x4& v0, const f32x4& v1) {
     return s16x8{(short)h_round16<BF>(v0[0]), (short)h_round16<BF>(v0[1]), (short)h_round16<BF>(v0[2]), (short)h_round16<BF>(v0[3]),

@@ -12,6 +12,7 @@
 
 #include "launch.h"
 #include "params.h"
+#include "round16.h"
 
 namespace ctamd {
 
@@ -46,6 +47,13 @@ template <> __device__ __forceinline__ double gs_load<__hip_bfloat16>(const __hi
 template <typename T> __device__ __forceinline__ void gs_store(T* p, double v) { *p = (T)v; }
 template <> __device__ __forceinline__ void gs_store<__half>(__half* p, double v) { *p = __float2half((float)v); }
 template <> __device__ __forceinline__ void gs_store<__hip_bfloat16>(__hip_bfloat16* p, double v) { *p = __float2bfloat16((float)v); }
+// *d = val + beta * *c in the precision S, stored as T; fp16: the sum rounded once, straight to 16 bits (round16.h)
+template <typename T, typename S> __device__ __forceinline__ void gs_store_with_c(T* d, S val, S beta, const T* c) {
+    gs_store<T>(d, (double)(val + beta * (S)gs_load<T>(c)));
+}
+template <> __device__ __forceinline__ void gs_store_with_c<__half, float>(__half* d, float val, float beta, const __half* c) {
+    *reinterpret_cast<uint16_t*>(d) = h_round16_with_c<false>(val, beta, *reinterpret_cast<const uint16_t*>(c));
+}
 
 template <typename T, typename S>
 __global__ void __launch_bounds__(256) gett_simple_kernel(const GettParams p) {
@@ -86,10 +94,10 @@ __global__ void __launch_bounds__(256) gett_simple_kernel(const GettParams p) {
     if (!okM || !okN) return;
     const S alpha = sizeof(S) == 8 ? (S)p.alpha64 : (S)p.alpha;
     const S beta  = sizeof(S) == 8 ? (S)p.beta64 : (S)p.beta;
-    S val = alpha * acc;
-    if (beta != (S)0)
-        val += beta * (S)gs_load<T>(C + gs_offset_c(p.gM, p.cStrideM, m) + gs_offset_c(p.gN, p.cStrideN, n));
-    gs_store<T>(D + gs_offset<1>(p.gM, m) + gs_offset<1>(p.gN, n), (double)val);
+    const S val = alpha * acc;
+    T* d = D + gs_offset<1>(p.gM, m) + gs_offset<1>(p.gN, n);
+    if (beta != (S)0) gs_store_with_c<T, S>(d, val, beta, C + gs_offset_c(p.gM, p.cStrideM, m) + gs_offset_c(p.gN, p.cStrideN, n));
+    else gs_store<T>(d, (double)val);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -127,9 +135,9 @@ __global__ void __launch_bounds__(256) gett_wide_kernel(const WideParams p) {
     }
     const S alpha = sizeof(S) == 8 ? (S)p.alpha64 : (S)p.alpha;
     const S beta  = sizeof(S) == 8 ? (S)p.beta64 : (S)p.beta;
-    S val = alpha * acc;
-    if (beta != (S)0) val += beta * (S)gs_load<T>(static_cast<const T*>(p.C) + oC);
-    gs_store<T>(static_cast<T*>(p.D) + oD, (double)val);
+    const S val = alpha * acc;
+    if (beta != (S)0) gs_store_with_c<T, S>(static_cast<T*>(p.D) + oD, val, beta, static_cast<const T*>(p.C) + oC);
+    else gs_store<T>(static_cast<T*>(p.D) + oD, (double)val);
 }
 
 // Complex data: D = alpha * op(A) * op(B) + beta * op(C) with op = identity or conjugate

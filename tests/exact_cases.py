@@ -326,12 +326,12 @@ def _dt(ct, name):
     return {"bfloat16": ct.R_16BF, "float16": ct.R_16F, "float32": ct.R_32F, "float64": ct.R_64F, "complex64": ct.C_32F, "complex128": ct.C_64F}[name]
 
 
-def _data(case, swap):
-    key = (case.data_key, swap, case.pad[:2], case.off)
+def _data(case, swap, make=xd.make_exact):
+    key = (case.data_key, swap, case.pad[:2], case.off, make.__name__)
     if key not in _DATA:
         if len(_DATA) >= 2:
             _DATA.clear()
-        A, B, C = xd.make_exact(case, swap)
+        A, B, C = make(case, swap)
         frac = xd.check_draw(case, A, B, C, swap)
         pa, pb = Placed(case.extents(case.modes[0]), case.dtype, case.pad[0], case.off), Placed(case.extents(case.modes[1]), case.dtype, case.pad[1], case.off)
         pa.set(A)
@@ -364,8 +364,11 @@ def plan_path(ct, ops, h, case):
     return d
 
 
-def run_contraction_case(ct, ops, h, case):
+def run_contraction_case(ct, ops, h, case, make=xd.make_exact, expect=xd.expected, stats=None):
+    """`make` draws the data and `expect` turns the exact reference into (what a correct kernel stores, a figure for the report): the
+    exact regime of tests/exact_data.py unless given (tests/rounding_data.py: the rounding regime, with a report of its own in `stats`)"""
     import torch
+    stats = STATS if stats is None else stats
     with wc.hook_env(case):
         plan = _plan(ct, ops, h, case)
     try:
@@ -373,13 +376,13 @@ def run_contraction_case(ct, ops, h, case):
         assert case.expect(d) and case.gpu_expect(d), "%s is off its path: %s" % (case.id, d)
         ws = torch.empty(max(plan.required_workspace, 256), dtype=torch.uint8, device="cuda")
         for swap in (False, True):
-            dat = _data(case, swap)
+            dat = _data(case, swap, make)
             A, B, C = dat["host"]
             pa, pb = dat["dev"]
             rk = (case.alpha, case.beta, case.conjA, case.conjB, case.conjC)
             if rk not in dat["ref"]:
                 ref = xd.exact_reference(case, A, B, C, device="cuda")
-                dat["ref"][rk] = xd.expected(case, ref)
+                dat["ref"][rk] = expect(case, ref)
             want, share = dat["ref"][rk]
             pd = Placed(case.extents(case.modes[2]), case.dtype, case.pad[2], case.off)          # D: NaN everywhere
             pc = None
@@ -392,7 +395,7 @@ def run_contraction_case(ct, ops, h, case):
             xd.assert_exact(pd.get(), want, what)
             pd.check_outside(what)
             m = xd.Modes(*case.modes[:3])
-            STATS.append((case.dtype, int(xd.np.prod([case.ext[c] for c in m.K])) if m.K else 1, dat["frac"], share))
+            stats.append((case.dtype, int(xd.np.prod([case.ext[c] for c in m.K])) if m.K else 1, dat["frac"], share))
     finally:
         plan.destroy()
     return d

@@ -248,9 +248,10 @@ def _placed(case, t):
     return HostPlaced(case.extents(t), case.dtype, off=case.off, strides=case.strides(t))
 
 
-def run_case(ct, ops, h, case):
+def run_case(ct, ops, h, case, make=None, check=None, expect=None, runs=None):
     """ew_exact_cases.run_case on HostPlaced buffers; A is checked unchanged too"""
     import torch
+    make, check, expect = make or ew.make_draw, check or ew.check_draw, expect or ew.expected
     plan = make_plan(ct, ops, h, case)
     try:
         desc = wc.describe(ct, plan)
@@ -258,13 +259,13 @@ def run_case(ct, ops, h, case):
         d = {k: v for k, v in desc.pairs}
         ws = torch.empty(max(plan.required_workspace, 256), dtype=torch.uint8, device="cuda")
         for draw in range(ew.n_draws(case, d)):
-            ins = ew.make_draw(case, draw, d)
+            ins = make(case, draw, d)
             pa = _placed(case, "A")
             pa.set(ew._host(case, ins["A"]))
-            for run in case.runs:
+            for run in (runs or case.runs):
                 scal, cmode = run
-                ew.check_draw(case, ins, run, d)
-                want = ew.expected(case, reference(case, ins, run))
+                check(case, ins, run, d)
+                want = expect(case, reference(case, ins, run))
                 pd = _placed(case, "D")                                     # NaN everywhere
                 pc = None
                 if cmode == "inplace":
